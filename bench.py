@@ -35,6 +35,11 @@ Other workloads (parity-checked elsewhere; here for DESIGN.md's numbers):
   --workload real4096      Radix2Fft.forward semantics (real in, 12 B/sample)
   --workload fft4096_f64   configs[2]'s shape in f64 (32 B/sample)
   --workload fft16k / spectrum256 / peaks16k / single1024 (configs[1], latency) / stream, hostbatch (PCIe-inclusive)
+
+`--dump-outputs DIR` (the batched workloads): after the timed steps, what the last step computed -- the arrays a caller
+of the timed path receives -- is written as DIR/<name>.npy (float32, or float64 in the f64 workload), at most DUMP_BYTES
+in all: every row when they fit, else the rows of dump_rows(), a fixed seeded sample.  The inputs are seeded too, so
+two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -56,6 +61,38 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6290 me
 
 PLANES_ARENA_NOTE = ("BatchedFft.alloc_planes: one allocation of 80 GiB + a plane, input planes back to back at its start, "
                      "output planes 40 and 80 GiB in (each in a 32-GiB region of its own: DESIGN section 5)")
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: the most array bytes written (a seeded row sample of larger outputs)
+DUMP_SEED = 4242
+
+
+def dump_rows(rows: int, row_bytes: int) -> torch.Tensor:
+    """The output rows --dump-outputs writes: all `rows` when they fit in DUMP_BYTES, else a sorted sample drawn by a
+    CPU generator seeded with DUMP_SEED -- the same rows on every run with the same shape."""
+    k = min(rows, max(1, DUMP_BYTES // row_bytes))
+    if k == rows:
+        return torch.arange(rows)
+    g = torch.Generator()
+    g.manual_seed(DUMP_SEED)
+    return torch.randperm(rows, generator=g)[:k].sort().values
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Writes out_dir/<name>.npy for every device tensor in `arrays` (same row count each, rows on dim 0; int32 peak
+    indices become float64, exactly), the rows of dump_rows() only.  Returns the line's `dump_outputs` record."""
+    rows = next(iter(arrays.values())).shape[0]
+    host_dtype = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.float64}
+    row_bytes = sum(t[0].numel() * np.dtype(host_dtype[t.dtype]).itemsize for t in arrays.values())
+    sel = dump_rows(rows, row_bytes)
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, t in arrays.items():
+        a = t[sel.to(t.device)].cpu().numpy().astype(host_dtype[t.dtype])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        files[name] = list(a.shape)
+    rows_note = f"all {rows} rows" if len(sel) == rows else \
+        f"{len(sel)} of {rows} rows: torch.randperm({rows}, CPU generator seeded {DUMP_SEED})[:{len(sel)}], sorted"
+    return {"dir": out_dir, "files": files, "rows": rows_note}
 
 
 def synth_batch(batch: int, n: int, device, seed: int = 1337, complex_noise: bool = True):
@@ -589,7 +626,13 @@ def parse_args(argv):
                          "same way (`new_group(backend='nccl', device_id=...)`), all_gather_into_tensor on the real output "
                          "planes and on the 16-byte peak records, an orderly destroy: what one card can prove about the leg")
     ap.add_argument("--launch-timeout", type=float, default=900.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (rank 0's rows; "
+                         "a seeded sample when larger than DUMP_BYTES)")
     args = ap.parse_args(argv)
+    if args.dump_outputs is not None and (args.dry_run or args.workload in ("single1024", "stream", "hostbatch")):
+        ap.error("--dump-outputs needs one of the batched workloads (fft4096, fft4096_f64, real4096, fft16k, spectrum16k, "
+                 "spectrum256, peaks16k) and no --dry-run")
     under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
     if args.no_measure_traffic or under_profiler or os.environ.get("PDSP_BENCH_PMC_CHILD"):
         args.measure_traffic = False
@@ -761,10 +804,11 @@ def run_rank(args, world: int, rank: int, local: int) -> int:
         bytes_per_launch = (4 * n + 16) * chunk  # frame in, one 16-byte SpectrumPeak out
         kernel_name = kernel_label = "spectrum_dif16k_kernel<float, 2, true>"
         plan.window("hann")
+        peaks = [None]  # the last launch's records (--dump-outputs)
 
         def step():
             for _ in range(launches_per_step):
-                plan.spectrum_peaks(re, "hann", "one", 48000.0)
+                peaks[0] = plan.spectrum_peaks(re, "hann", "one", 48000.0)
     else:
         chunk = min(args.chunk if args.workload == "spectrum16k" else (1 << 20), per_gpu)  # ~1 GiB of frames per launch
         assert per_gpu % chunk == 0
@@ -823,6 +867,16 @@ def run_rank(args, world: int, rank: int, local: int) -> int:
     barrier()
     step_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
     clocks_after = read_clocks(dev) if rank == 0 else None
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:  # before the legs below reuse the output planes
+        if args.workload == "peaks16k":
+            idx, freq, pamp, pph = peaks[0][:4]
+            arrays = {"peak_index": idx, "peak_frequency": freq, "peak_amplitude": pamp, "peak_phase": pph}
+        elif parity_kind == "spectrum":
+            arrays = {"amplitude": amp}
+        else:
+            arrays = {"out_re": ore, "out_im": oim}
+        dumped = dump_outputs(args.dump_outputs, arrays)
 
     elapsed = max_over_ranks(elapsed_local)
     launch_ms = float(np.mean(step_ms)) / launches_per_step
@@ -905,6 +959,8 @@ def run_rank(args, world: int, rank: int, local: int) -> int:
                        "device_copy_under_load": copy_clocks,
                        "source": "sysfs pp_dpm_* and hwmon of /sys/class/drm/card*/device"},
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if args.measure_traffic and world == 1:
             nbytes, detail = traffic_measured(args, kernel_name)
             if nbytes is not None:
