@@ -30,8 +30,8 @@ thread_local std::string g_err;
 // development switches (tools / tests): 0 routes N = 16384 spectra to spectrum_packed_kernel<13>,
 // and 32 <= N <= 256 transforms to the direct kernel instead of fft_staged_kernel
 int g_split16k = 1;
-int g_fused_window = 1;
-int g_twopass = 1;       // pdsp_set_twopass: 2^15 <= N <= 2^18 f32 transforms in two passes (balanced factors)  // pdsp_set_fused_window: plan-owned cosine-sum windows evaluated in the kernel
+int g_fused_window = 1;  // pdsp_set_fused_window: plan-owned cosine-sum windows evaluated in the kernel
+int g_twopass = 1;       // pdsp_set_twopass: 2^15 <= N <= 2^18 f32 transforms in two passes (balanced factors)
 int g_split8k_f32 = 0;  // f32 N = 8192 rows on fft_split2_kernel too (A/B: pdsp_set_split16k bit 1)
 int g_staged_small = 1;
 int g_real_packed = 1;  // pdsp_set_real_packed: Radix2Fft.forward rows of 512 <= N <= 16384 on fft_real_kernel

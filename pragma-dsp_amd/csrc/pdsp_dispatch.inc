@@ -1,11 +1,63 @@
 // pdsp_dispatch.inc -- kernel dispatch by size and call shape (templates on the scalar type T), included by the
 // kernel translation units (pdsp_kernels_*.hip), which instantiate it explicitly; see pdsp_internal.h.
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "pdsp_internal.h"
 
 namespace pdsp_host {
+
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// A runtime int as a template argument: returns f(int_c<v>{}) for Lo <= v <= Hi and `outside` otherwise.  Only
+// the instances Lo ... Hi are compiled, so the range is the set of kernels built.
+template <int Lo, int Hi, class R, class F>
+R with_int(int v, R outside, const F &f) {
+  if constexpr (Lo <= Hi) {
+    if (v == Lo) return f(int_c<Lo>{});
+    return with_int<Lo + 1, Hi>(v, outside, f);
+  } else {
+    return outside;
+  }
+}
+
+// Are all the pointers multiples of `bytes` (a power of two)?  Null pointers are.
+template <class... P>
+bool aligned(size_t bytes, const P *...p) {
+  return (((uintptr_t)p | ...) & (bytes - 1)) == 0;
+}
+
+// A window that is one of the plan's own tables (pdsp_plan_window_f32) is known by kind (-1: the caller's table;
+// PDSP_WIN_RECT is all ones).  With `fuse`, the kinds that are cosine sums w = k0 + k1 cos(f n) + k2 cos^2(f n)
+// get their coefficients and term count (2 / 3; 0: not fused), for the kernels that evaluate them in registers.
+struct WindowKind {
+  int kind = -1, terms = 0;
+  float k0 = 0.f, k1 = 0.f, k2 = 0.f;
+};
+template <typename T>
+WindowKind window_kind(const Tables<T> &t, const T *window, bool fuse) {
+  WindowKind w;
+  for (int k = 0; k < 4; ++k)
+    if (window && window == t.win[k]) w.kind = k;
+  if (!fuse) return w;
+  if (w.kind == PDSP_WIN_HANN) w.terms = 2, w.k0 = 0.5f, w.k1 = -0.5f;
+  else if (w.kind == PDSP_WIN_HAMMING) w.terms = 2, w.k0 = 0.54f, w.k1 = -0.46f;
+  else if (w.kind == PDSP_WIN_BLACKMAN) w.terms = 3, w.k0 = 0.42f - 0.08f, w.k1 = -0.5f, w.k2 = 2 * 0.08f;
+  return w;
+}
+
+// Peaks-only output: the amplitude / phase rows the peak kernels read but the caller did not ask for live in
+// scratch, `rows` values each.  peak_rows_extra: the values that takes; place_peak_rows points amp / ph at them.
+inline size_t peak_rows_extra(const void *peaks, const void *amp, const void *ph, size_t rows) {
+  return (peaks && !amp ? rows : 0) + (peaks && !ph ? rows : 0);
+}
+template <typename T>
+void place_peak_rows(const void *peaks, T *&amp, T *&ph, T *at, size_t rows) {
+  if (peaks && !amp) amp = at, at += rows;
+  if (peaks && !ph) ph = at;
+}
 
 template <typename T, int LOG2N, class LD, class ST>
 hipError_t launch_one(const LD &ld, const ST &st, const typename pdsp::vec2<T>::type *tw, long long batch,
@@ -24,16 +76,7 @@ hipError_t launch_one(const LD &ld, const ST &st, const typename pdsp::vec2<T>::
 template <typename T, class LD, class ST>
 hipError_t launch_fft(int log2n, const LD &ld, const ST &st, const typename pdsp::vec2<T>::type *tw, long long batch,
                       hipStream_t s) {
-  switch (log2n) {
-#define PDSP_CASE(L) \
-  case L:            \
-    return launch_one<T, L>(ld, st, tw, batch, s);
-    PDSP_CASE(0) PDSP_CASE(1) PDSP_CASE(2) PDSP_CASE(3) PDSP_CASE(4) PDSP_CASE(5) PDSP_CASE(6) PDSP_CASE(7)
-    PDSP_CASE(8) PDSP_CASE(9) PDSP_CASE(10) PDSP_CASE(11) PDSP_CASE(12) PDSP_CASE(13) PDSP_CASE(14)
-#undef PDSP_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  return with_int<0, 14>(log2n, hipErrorInvalidValue, [&](auto L) { return launch_one<T, L>(ld, st, tw, batch, s); });
 }
 
 // The same for N <= 32 only (spectrum() of frames below the packed-real path's sizes: LoadFrameWindowed /
@@ -41,15 +84,7 @@ hipError_t launch_fft(int log2n, const LD &ld, const ST &st, const typename pdsp
 template <typename T, class LD, class ST>
 hipError_t launch_fft_small(int log2n, const LD &ld, const ST &st, const typename pdsp::vec2<T>::type *tw, long long batch,
                             hipStream_t s) {
-  switch (log2n) {
-#define PDSP_CASE(L) \
-  case L:            \
-    return launch_one<T, L>(ld, st, tw, batch, s);
-    PDSP_CASE(0) PDSP_CASE(1) PDSP_CASE(2) PDSP_CASE(3) PDSP_CASE(4) PDSP_CASE(5)
-#undef PDSP_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  return with_int<0, 5>(log2n, hipErrorInvalidValue, [&](auto L) { return launch_one<T, L>(ld, st, tw, batch, s); });
 }
 
 // Rows of planar complex points: N = 16384 (f32) goes to fft_split4_kernel when the input planes
@@ -86,70 +121,46 @@ hipError_t launch_packed_one(bool fast, const T *frames, const T *win, int wmode
   using TR = pdsp::FftTraits<LOG2M, pdsp::packed_log2e(LOG2M)>;
   const long long ngroups = (batch + TR::ROWS - 1) / TR::ROWS;
   const dim3 block(TR::WG);
-#define PDSP_LAUNCH(F, W, P)                                                                                  \
-  hipLaunchKernelGGL((pdsp::spectrum_packed_kernel<T, LOG2M, F, W, P>), dim3((unsigned)ngroups), block, 0, s, \
-                     frames, win, wf, frame_len, stride, tw, twr, amp, ph, two_sided, s_edge, s_mid, peaks, freq_scale, \
-                     batch)
-#define PDSP_LAUNCH_FW(F, W)                            \
-  do {                                                  \
-    if constexpr (sizeof(T) == 4) {                     \
-      if (peaks) PDSP_LAUNCH(F, W, true);               \
-      else PDSP_LAUNCH(F, W, false);                    \
-    } else {                                            \
-      PDSP_LAUNCH(F, W, false); /* fused peaks: f32 only */ \
-    }                                                   \
-  } while (0)
+  auto launch = [&](auto fast_c, auto win_c) {
+    auto go = [&](auto peak_c) {
+      hipLaunchKernelGGL((pdsp::spectrum_packed_kernel<T, LOG2M, fast_c, win_c, peak_c>), dim3((unsigned)ngroups), block,
+                         0, s, frames, win, wf, frame_len, stride, tw, twr, amp, ph, two_sided, s_edge, s_mid, peaks,
+                         freq_scale, batch);
+    };
+    if constexpr (sizeof(T) == 4) {
+      if (peaks) go(std::true_type{});
+      else go(std::false_type{});
+    } else {
+      go(std::false_type{});  // fused peaks: f32 only
+    }
+    return hipGetLastError();
+  };
   // fused cosine-sum windows (wmode 2 / 3): whole f32 frames of N = 1024 ... 8192 (the sizes whose plans
   // carry the angle-addition tables); everything else reads the window as a table
   if constexpr (sizeof(T) == 4 && LOG2M >= 9 && LOG2M <= 12) {
-    if (fast && wmode == 2) {
-      PDSP_LAUNCH_FW(true, 2);
-      return hipGetLastError();
-    }
-    if (fast && wmode == 3) {
-      PDSP_LAUNCH_FW(true, 3);
-      return hipGetLastError();
-    }
+    if (fast && wmode == 2) return launch(std::true_type{}, int_c<2>{});
+    if (fast && wmode == 3) return launch(std::true_type{}, int_c<3>{});
   }
-  if (fast && win) PDSP_LAUNCH_FW(true, 1);
-  else if (fast) PDSP_LAUNCH_FW(true, 0);
-  else if (win) PDSP_LAUNCH_FW(false, 1);
-  else PDSP_LAUNCH_FW(false, 0);
-#undef PDSP_LAUNCH_FW
-#undef PDSP_LAUNCH
-  return hipGetLastError();
+  if (fast && win) return launch(std::true_type{}, int_c<1>{});
+  if (fast) return launch(std::true_type{}, int_c<0>{});
+  if (win) return launch(std::false_type{}, int_c<1>{});
+  return launch(std::false_type{}, int_c<0>{});
 }
 
 template <typename T, class... A>
 hipError_t launch_packed(int log2m, A... a) {
-  switch (log2m) {
-#define PDSP_CASE(L) \
-  case L:            \
-    return launch_packed_one<T, L>(a...);
-    PDSP_CASE(5) PDSP_CASE(6) PDSP_CASE(7) PDSP_CASE(8) PDSP_CASE(9) PDSP_CASE(10) PDSP_CASE(11) PDSP_CASE(12)
-    PDSP_CASE(13)
-#undef PDSP_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  return with_int<5, 13>(log2m, hipErrorInvalidValue, [&](auto L) { return launch_packed_one<T, L>(a...); });
 }
 
 template <typename T>
 hipError_t launch_real(int log2m, const T *x, T *ore, T *oim, T scale, const typename pdsp::vec2<T>::type *tw,
                        const typename pdsp::vec2<T>::type *twr, long long batch, hipStream_t s) {
-  switch (log2m) {
-#define PDSP_CASE(L)                                                                                              \
-  case L: {                                                                                                       \
-    using TR = pdsp::FftTraits<L, 4>;                                                                             \
-    hipLaunchKernelGGL((pdsp::fft_real_kernel<T, L>), dim3((unsigned)((batch + TR::ROWS - 1) / TR::ROWS)), dim3(TR::WG), \
-                       0, s, x, ore, oim, scale, tw, twr, batch);                                                 \
-    return hipGetLastError();                                                                                     \
-  }
-    PDSP_CASE(12) PDSP_CASE(13)
-#undef PDSP_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+  return with_int<12, 13>(log2m, hipErrorInvalidValue, [&](auto L) {
+    using TR = pdsp::FftTraits<L, 4>;
+    hipLaunchKernelGGL((pdsp::fft_real_kernel<T, L>), dim3((unsigned)((batch + TR::ROWS - 1) / TR::ROWS)), dim3(TR::WG),
+                       0, s, x, ore, oim, scale, tw, twr, batch);
+    return hipGetLastError();
+  });
 }
 
 // Four-step transform of `batch` rows of N = N1*N2 points into scratch planes (pass A + B);
@@ -160,27 +171,20 @@ int fourstep_ab(const pdsp_plan *plan, long long batch, const T *re_in, const T 
   const Tables<T> &t = tables<T>(plan);
   const int n2 = 1 << t.log2n2;
   const long long blocks = batch * (n2 / 256);
-  if (blocks > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+  if (int rc = check_grid(blocks, batch)) return rc;
   const pdsp::cx<T> *twa = reinterpret_cast<const pdsp::cx<T> *>(t.twa);
   const pdsp::cx<T> *twb = reinterpret_cast<const pdsp::cx<T> *>(t.twb);
-#define PDSP_COLS(L, R, W)                                                                                        \
-  hipLaunchKernelGGL((pdsp::fourstep_cols_kernel<T, L, R, W>), dim3((unsigned)blocks), dim3(256), 0, s, re_in, im_in, \
-                     win, s_re, s_im, twa, twb, n2, in_stride, frame_len, batch)
-#define PDSP_COLS_L(L)                     \
-  do {                                     \
-    if (im_in) PDSP_COLS(L, false, false); \
-    else if (win) PDSP_COLS(L, true, true); \
-    else PDSP_COLS(L, true, false);        \
-  } while (0)
-  switch (t.log2n1) {
-    case 1: PDSP_COLS_L(1); break;
-    case 2: PDSP_COLS_L(2); break;
-    case 3: PDSP_COLS_L(3); break;
-    case 4: PDSP_COLS_L(4); break;
-    default: return fail(PDSP_ERR_UNSUPPORTED_SIZE, "unsupported four-step split");
-  }
-#undef PDSP_COLS_L
-#undef PDSP_COLS
+  const bool known = with_int<1, 4>(t.log2n1, false, [&](auto L) {
+    auto go = [&](auto real_c, auto win_c) {
+      hipLaunchKernelGGL((pdsp::fourstep_cols_kernel<T, L, real_c, win_c>), dim3((unsigned)blocks), dim3(256), 0, s,
+                         re_in, im_in, win, s_re, s_im, twa, twb, n2, in_stride, frame_len, batch);
+    };
+    if (im_in) go(std::false_type{}, std::false_type{});
+    else if (win) go(std::true_type{}, std::true_type{});
+    else go(std::true_type{}, std::false_type{});
+    return true;
+  });
+  if (!known) return fail(PDSP_ERR_UNSUPPORTED_SIZE, "unsupported four-step split");
   PDSP_HIP_TRY(hipGetLastError());
   // pass B: the N1 * batch rows of N2 points, in place (each workgroup loads its row before it stores)
   pdsp::LoadComplex<T> ld{s_re, s_im, n2};
@@ -195,17 +199,12 @@ int fourstep_c(const pdsp_plan *plan, long long batch, const T *s_re, const T *s
   const Tables<T> &t = tables<T>(plan);
   const int n2 = 1 << t.log2n2;
   const long long blocks = batch * (n2 / 256);
-#define PDSP_OUT(L)                                                                                              \
-  hipLaunchKernelGGL((pdsp::fourstep_out_kernel<T, L, MODE>), dim3((unsigned)blocks), dim3(256), 0, s, s_re, s_im, o1, \
-                     o2, n2, scale, bins, nyq, s_edge, s_mid, batch)
-  switch (t.log2n1) {
-    case 1: PDSP_OUT(1); break;
-    case 2: PDSP_OUT(2); break;
-    case 3: PDSP_OUT(3); break;
-    case 4: PDSP_OUT(4); break;
-    default: return fail(PDSP_ERR_UNSUPPORTED_SIZE, "unsupported four-step split");
-  }
-#undef PDSP_OUT
+  const bool known = with_int<1, 4>(t.log2n1, false, [&](auto L) {
+    hipLaunchKernelGGL((pdsp::fourstep_out_kernel<T, L, MODE>), dim3((unsigned)blocks), dim3(256), 0, s, s_re, s_im,
+                       o1, o2, n2, scale, bins, nyq, s_edge, s_mid, batch);
+    return true;
+  });
+  if (!known) return fail(PDSP_ERR_UNSUPPORTED_SIZE, "unsupported four-step split");
   PDSP_HIP_TRY(hipGetLastError());
   return PDSP_OK;
 }
@@ -215,18 +214,11 @@ template <typename T>
 hipError_t launch_staged_complex(int log2n, const pdsp::LoadComplex<T> &ld, const pdsp::StoreComplex<T> &st,
                                  const typename pdsp::vec2<T>::type *tw, long long rows, hipStream_t s) {
   const long long blocks = ((rows << log2n) + 4095) / 4096;
-#define PDSP_STAGED_C(L)                                                                                  \
-  hipLaunchKernelGGL((pdsp::fft_staged_kernel<T, L, pdsp::LoadComplex<T>, pdsp::StoreComplex<T>>),         \
-                     dim3((unsigned)blocks), dim3(256), 0, s, ld, st, tw, rows)
-  switch (log2n) {
-    case 5: PDSP_STAGED_C(5); break;
-    case 6: PDSP_STAGED_C(6); break;
-    case 7: PDSP_STAGED_C(7); break;
-    case 8: PDSP_STAGED_C(8); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef PDSP_STAGED_C
-  return hipGetLastError();
+  return with_int<5, 8>(log2n, hipErrorInvalidValue, [&](auto L) {
+    hipLaunchKernelGGL((pdsp::fft_staged_kernel<T, L, pdsp::LoadComplex<T>, pdsp::StoreComplex<T>>),
+                       dim3((unsigned)blocks), dim3(256), 0, s, ld, st, tw, rows);
+    return hipGetLastError();
+  });
 }
 
 // findPeak over stored amplitude rows: index array and/or SpectrumPeak records.
@@ -251,24 +243,12 @@ template <typename T, bool AMP, class LD>
 hipError_t launch_tiny(int log2n, const LD &ld, const T *win, T *o1, T *o2, T scale, int bins, int nyq, T s_edge,
                        T s_mid, long long batch, hipStream_t s) {
   const long long blocks = ((batch << log2n) + 4095) / 4096;
-#define PDSP_TINY(L)                                                                                             \
-  hipLaunchKernelGGL((pdsp::fft_tiny_staged_kernel<T, L, AMP, LD>), dim3((unsigned)blocks), dim3(256), 0, s, ld, win, \
-                     o1, o2, scale, bins, nyq, s_edge, s_mid, batch)
-  switch (log2n) {
-    case 1: PDSP_TINY(1); break;
-    case 2: PDSP_TINY(2); break;
-    case 3: PDSP_TINY(3); break;
-    case 4: PDSP_TINY(4); break;
-    case 5:
-      if constexpr (AMP) {  // N = 32 transforms have fft_staged_kernel; the spectrum of N = 32 frames comes here
-        PDSP_TINY(5);
-        break;
-      }
-      return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-  }
-#undef PDSP_TINY
-  return hipGetLastError();
+  // N = 32 transforms have fft_staged_kernel; the spectrum of N = 32 frames comes here
+  return with_int<1, AMP ? 5 : 4>(log2n, hipErrorInvalidValue, [&](auto L) {
+    hipLaunchKernelGGL((pdsp::fft_tiny_staged_kernel<T, L, AMP, LD>), dim3((unsigned)blocks), dim3(256), 0, s, ld, win,
+                       o1, o2, scale, bins, nyq, s_edge, s_mid, batch);
+    return hipGetLastError();
+  });
 }
 
 // General four-step path (log2n1 > kMaxLog2N1), steps 1-4 of bigfft_transpose_kernel's header:
@@ -324,7 +304,7 @@ int tile_pass(int l, int real_in, const T *in_re, const T *in_im, T *out_re, T *
               const typename pdsp::vec2<T>::type *tw, const Tables<T> &t, pdsp::TileGeom g, T scale, long long batch,
               hipStream_t s) {
   const long long blocks = batch * g.nblk * g.tiles;
-  if (blocks > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+  if (int rc = check_grid(blocks, batch)) return rc;
   const pdsp::cx<T> *twa = reinterpret_cast<const pdsp::cx<T> *>(t.twa);
   const pdsp::cx<T> *twb = reinterpret_cast<const pdsp::cx<T> *>(t.twb);
   if constexpr (COLS && sizeof(T) == 4) {
@@ -355,43 +335,25 @@ int tile_pass(int l, int real_in, const T *in_re, const T *in_im, T *out_re, T *
       return PDSP_OK;
     }
   }
-#define PDSP_TILE_IN(L, TILE, IN)                                                                                  \
-  hipLaunchKernelGGL((pdsp::tile_pass_kernel<T, L, TILE, COLS, ((COLS && (IN < 5 || sizeof(T) == 4)) ? IN : 0)>),    \
-                     dim3((unsigned)blocks), dim3(256),                                                               \
-                     0, s, in_re, in_im, out_re, out_im, tw, twa, twb, g, scale, batch)
-#define PDSP_TILE(L, TILE)                                 \
-  do {                                                     \
-    switch (COLS ? real_in : 0) {                          \
-      case 1: PDSP_TILE_IN(L, TILE, 1); break;             \
-      case 2: PDSP_TILE_IN(L, TILE, 2); break;             \
-      case 3: PDSP_TILE_IN(L, TILE, 3); break;             \
-      case 4: PDSP_TILE_IN(L, TILE, 4); break;             \
-      case 5: PDSP_TILE_IN(L, TILE, 5); break;             \
-      case 6: PDSP_TILE_IN(L, TILE, 6); break;             \
-      default: PDSP_TILE_IN(L, TILE, 0); break;            \
-    }                                                      \
-  } while (0)
-  switch (l) {
-    case 6: PDSP_TILE(6, 64); break;
-    case 7: PDSP_TILE(7, 32); break;
-    case 8: PDSP_TILE(8, 32); break;
-    case 9: PDSP_TILE(9, 16); break;
-    default: return fail(PDSP_ERR_UNSUPPORTED_SIZE, "unsupported tile-pass factor 2^%d", l);
-  }
-#undef PDSP_TILE
-#undef PDSP_TILE_IN
+  const bool known = with_int<6, 9>(l, false, [&](auto L) {
+    auto go = [&](auto in_c) {
+      // IN = 0 for row passes; f64 has no fused-window first pass (IN 5 / 6)
+      constexpr int IN = (COLS && (in_c < 5 || sizeof(T) == 4)) ? in_c : 0;
+      hipLaunchKernelGGL((pdsp::tile_pass_kernel<T, L, tile_width(L), COLS, IN>), dim3((unsigned)blocks), dim3(256), 0,
+                         s, in_re, in_im, out_re, out_im, tw, twa, twb, g, scale, batch);
+      return true;
+    };
+    return COLS && real_in >= 1 && real_in <= 6 ? with_int<1, 6>(real_in, false, go) : go(int_c<0>{});
+  });
+  if (!known) return fail(PDSP_ERR_UNSUPPORTED_SIZE, "unsupported tile-pass factor 2^%d", l);
   PDSP_HIP_TRY(hipGetLastError());
   return PDSP_OK;
 }
 
-// Two or three tile passes (tile_pass_kernel's header): 2^15 <= N <= 2^27, f32, 16-byte aligned
-// planes.  s1 / s2: scratch plane pairs ((re, im) each); s2 is only used by the three-pass form.  Every
-// pass reads one pair and writes another, so input and output may alias each other.
-// `window` (real input only): applyWindow on the first pass's load; in_batch: distance between input rows.
 // The pass chain on one set of factor tables: `n` points per transform, np factors 2^l[i] with radix tables tw[i];
 // tshift = 1 when t.twa / t.twb belong to the 2n-point plan.  `first` = tile_pass_kernel's IN for the first pass
 // (im_in then carries the window table or nothing); in_batch = distance between input rows (real samples for
-// first >= 1).
+// first >= 1).  Scratch pairs s1 / s2 as for tilepass_complex below.
 template <typename T>
 int tilepass_chain(const Tables<T> &t, long long n, int np, const int *l, typename pdsp::vec2<T>::type *const *tw,
                    unsigned tshift, int first, long long batch, const T *re_in, const T *im_in, long long in_batch,
@@ -480,7 +442,7 @@ int run_complex(const pdsp_plan *plan, long long batch, const T *re_in, const T 
   // Rows aligned to a sample pair.
   if constexpr (sizeof(T) == 8) {
     if (!im_in && g_real_packed && (plan->log2n == 13 || (plan->log2n == 14 && batch >= 8)) && t.tw_half && t.twr &&
-        ((uintptr_t)re_in & (2 * sizeof(T) - 1)) == 0) {
+        aligned(2 * sizeof(T), re_in)) {
       PDSP_HIP_TRY(launch_real<T>(plan->log2n - 1, re_in, re_out, im_out, scale, t.tw_half, t.twr, batch, s));
       return PDSP_OK;
     }
@@ -490,32 +452,30 @@ int run_complex(const pdsp_plan *plan, long long batch, const T *re_in, const T 
     // XCD's L2 (fft_paired_kernel).  In place the siblings would overwrite each other's input: tile passes then.
     // pdsp_set_twopass: any value but 1 keeps the tile passes (5: their current form) -- A/B tests.
     if ((plan->log2n == 15 || plan->log2n == 16) && g_twopass == 1 && t.tw12 && t.tws4 && t.twa && t.twb &&
-        (((uintptr_t)re_in | (uintptr_t)im_in | (uintptr_t)re_out | (uintptr_t)im_out) & 15) == 0) {
+        aligned(16, re_in, im_in, re_out, im_out)) {
       if (!planes_overlap(re_in, im_in, re_out, im_out, (size_t)batch * (size_t)plan->n * sizeof(T))) {
         const int lp = plan->log2n - 14;
         const long long blocks = ((batch + 7) / 8) * 8 * (1LL << lp);
-        if (blocks > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+        if (int rc = check_grid(blocks, batch)) return rc;
         const pdsp::cx<T> *twa = reinterpret_cast<const pdsp::cx<T> *>(t.twa);
         const pdsp::cx<T> *twb = reinterpret_cast<const pdsp::cx<T> *>(t.twb);
-#define PDSP_PAIRED(LP, REAL)                                                                                        \
-  hipLaunchKernelGGL((pdsp::fft_paired_kernel<T, LP, REAL>), dim3((unsigned)blocks), dim3(256), 0, s, re_in, im_in, re_out, \
-                     im_out, t.tw12, t.tws4, twa, twb, scale, batch, pdsp::PairedPacked{})
-        if (lp == 1) {
-          if (im_in) PDSP_PAIRED(1, false);
-          else PDSP_PAIRED(1, true);
-        } else {
-          if (im_in) PDSP_PAIRED(2, false);
-          else PDSP_PAIRED(2, true);
-        }
-#undef PDSP_PAIRED
+        auto paired = [&](auto lp_c) {
+          auto go = [&](auto real_c) {
+            hipLaunchKernelGGL((pdsp::fft_paired_kernel<T, lp_c, real_c>), dim3((unsigned)blocks), dim3(256), 0, s,
+                               re_in, im_in, re_out, im_out, t.tw12, t.tws4, twa, twb, scale, batch, pdsp::PairedPacked{});
+          };
+          if (im_in) go(std::false_type{});
+          else go(std::true_type{});
+        };
+        if (lp == 1) paired(int_c<1>{});
+        else paired(int_c<2>{});
         PDSP_HIP_TRY(hipGetLastError());
         return PDSP_OK;
       }
     }
     // tile passes with balanced factors (two for 2^15..2^18, three for 2^19..2^27) where the tables exist and
     // every plane is 16-byte aligned; pdsp_set_twopass(0) keeps round 1's four-step forms (A/B tests)
-    if (t.tp_np && (g_twopass & 1) &&
-        (((uintptr_t)re_in | (uintptr_t)im_in | (uintptr_t)re_out | (uintptr_t)im_out) & 15) == 0) {
+    if (t.tp_np && (g_twopass & 1) && aligned(16, re_in, im_in, re_out, im_out)) {
       const size_t plane = (size_t)batch * (size_t)plan->n;
       const bool aliased = planes_overlap(re_in, im_in, re_out, im_out, plane * sizeof(T));
       // two passes: one scratch pair.  Three passes: the output planes double as the first scratch pair
@@ -551,8 +511,7 @@ int run_complex(const pdsp_plan *plan, long long batch, const T *re_in, const T 
     return rc;
   }
   hipError_t e;
-  const bool planes16 =
-      (((uintptr_t)re_in | (uintptr_t)im_in | (uintptr_t)re_out | (uintptr_t)im_out) & (4 * sizeof(T) - 1)) == 0;
+  const bool planes16 = aligned(4 * sizeof(T), re_in, im_in, re_out, im_out);
   if (plan->log2n >= 1 && plan->log2n <= 4 && g_staged_small && planes16) {  // 2 <= N <= 16: one thread per row
     if (im_in) {
       pdsp::LoadComplex<T> ld{re_in, im_in, plan->n};
@@ -566,33 +525,24 @@ int run_complex(const pdsp_plan *plan, long long batch, const T *re_in, const T 
   }
   pdsp::StoreComplex<T> st{re_out, im_out, plan->n, scale};
   // (f64 at N = 256: 69.6 KB of LDS per workgroup, the direct kernel measures 12 % faster)
-  if (plan->log2n >= 5 && plan->log2n <= (sizeof(T) == 4 ? 8 : 7) && g_staged_small &&
-      (((uintptr_t)re_in | (uintptr_t)im_in | (uintptr_t)re_out | (uintptr_t)im_out) & (4 * sizeof(T) - 1)) == 0) {
+  if (plan->log2n >= 5 && plan->log2n <= (sizeof(T) == 4 ? 8 : 7) && g_staged_small && planes16) {
     // small N: coalesced 16-byte I/O staged through LDS (fft_staged_kernel)
     const long long blocks = (batch * plan->n + 4095) / 4096;
-#define PDSP_STAGED(L)                                                                                         \
-  do {                                                                                                         \
-    if (im_in) {                                                                                               \
-      pdsp::LoadComplex<T> ld{re_in, im_in, plan->n};                                                          \
-      hipLaunchKernelGGL((pdsp::fft_staged_kernel<T, L, pdsp::LoadComplex<T>, pdsp::StoreComplex<T>>),          \
-                         dim3((unsigned)blocks), dim3(256), 0, s, ld, st, t.tw, batch);                        \
-    } else {                                                                                                   \
-      pdsp::LoadReal<T> ld{re_in, plan->n};                                                                    \
-      hipLaunchKernelGGL((pdsp::fft_staged_kernel<T, L, pdsp::LoadReal<T>, pdsp::StoreComplex<T>>),             \
-                         dim3((unsigned)blocks), dim3(256), 0, s, ld, st, t.tw, batch);                        \
-    }                                                                                                          \
-  } while (0)
-    switch (plan->log2n) {
-      case 5: PDSP_STAGED(5); break;
-      case 6: PDSP_STAGED(6); break;
-      case 7: PDSP_STAGED(7); break;
-      default: PDSP_STAGED(8); break;
-    }
-#undef PDSP_STAGED
+    auto staged = [&](auto L, const auto &ld) {
+      using LD = std::decay_t<decltype(ld)>;
+      hipLaunchKernelGGL((pdsp::fft_staged_kernel<T, L, LD, pdsp::StoreComplex<T>>), dim3((unsigned)blocks), dim3(256),
+                         0, s, ld, st, t.tw, batch);
+      return true;
+    };
+    // (the sizes 5 ... 8 are built for both types; f64 stops at 7 above)
+    with_int<5, 8>(plan->log2n, false, [&](auto L) {
+      if (im_in) return staged(L, pdsp::LoadComplex<T>{re_in, im_in, plan->n});
+      return staged(L, pdsp::LoadReal<T>{re_in, plan->n});
+    });
     PDSP_HIP_TRY(hipGetLastError());
     return PDSP_OK;
   }
-  const bool aligned16 = (((uintptr_t)re_in | (uintptr_t)im_in) & 15) == 0;
+  const bool aligned16 = aligned(16, re_in, im_in);
   if (im_in) {
     pdsp::LoadComplex<T> ld{re_in, im_in, plan->n};
     e = launch_rows<T>(t, plan->log2n, ld, st, batch, s, aligned16);
@@ -610,7 +560,7 @@ int run_interleaved(const pdsp_plan *plan, long long batch, const T *in, T *out,
   if (int rc = check_plan_batch(plan, batch)) return rc;
   if (batch == 0) return PDSP_OK;
   if (!in || !out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
-  if ((((uintptr_t)in | (uintptr_t)out) & (2 * sizeof(T) - 1)) != 0)
+  if (!aligned(2 * sizeof(T), in, out))
     return fail(PDSP_ERR_BAD_ARG, "interleaved rows must be aligned to one (re, im) pair");
   const Tables<T> &t = tables<T>(plan);
   if (!t.tw || t.log2n1 > 0)
@@ -636,9 +586,8 @@ template <int OP>
 int launch_complex_op(long long count, const float *are, const float *aim, const float *bre, const float *bim,
                       long long b_len, float sre, float sim, float *ore, float *oim, hipStream_t s) {
   const bool binary = OP <= pdsp::kDiv;
-  const uintptr_t align = (uintptr_t)are | (uintptr_t)aim | (uintptr_t)ore | (uintptr_t)oim |
-                          (binary ? ((uintptr_t)bre | (uintptr_t)bim) : 0);
-  const bool vec4 = (align & 15) == 0 && count % 4 == 0 && (!binary || b_len % 4 == 0);
+  const bool vec4 = aligned(16, are, aim, ore, oim) && (!binary || aligned(16, bre, bim)) && count % 4 == 0 &&
+                    (!binary || b_len % 4 == 0);
   if (vec4)
     hipLaunchKernelGGL((pdsp::complex_op_kernel<float, OP, 4>), dim3(grid_for(count / 4)), dim3(256), 0, s, are, aim,
                        bre, bim, sre, sim, ore, oim, count, b_len);
@@ -689,69 +638,53 @@ int spectrum_impl(const pdsp_plan *plan, long long batch, const T *frames, long 
     // bytes per sample: 4+4, 4+4 (, 4+4), 4+2 = 22 (30) where the four-step forms on (x*w, 0) move 38 (70).  The four-step forms stay for partial /
     // unaligned frames and f64.
     if (t.log2n1 > 0 && t.hp_np && (g_twopass & 1) && used == n && (frame_stride & 3) == 0 &&
-        (((uintptr_t)frames | (uintptr_t)window) & 15) == 0) {
+        aligned(16, frames, window)) {
       T *amp = amp_out, *ph = phase_out;
       const long long m = n / 2;
       const size_t plane = (size_t)batch * (size_t)m, rows = (size_t)batch * bins;
-      const size_t extra = (peaks_out && !amp ? rows : 0) + (peaks_out && !ph ? rows : 0);
       StreamScratch mem(stream);
-      PDSP_HIP_TRY(mem.alloc((4 * plane + extra) * sizeof(T)));
+      PDSP_HIP_TRY(mem.alloc((4 * plane + peak_rows_extra(peaks_out, amp, ph, rows)) * sizeof(T)));
       T *const sc = (T *)mem.p;
-      if (peaks_out && !amp) amp = sc + 4 * plane;
-      if (peaks_out && !ph) ph = sc + 4 * plane + (amp_out ? 0 : rows);
+      place_peak_rows(peaks_out, amp, ph, sc + 4 * plane, rows);
       // pass chain: frames -> s1 (-> s2) -> Z; two passes: Z = s2; three passes: Z = s1 again
       T *const s1_re = sc, *const s1_im = sc + plane, *const s2_re = sc + 2 * plane, *const s2_im = sc + 3 * plane;
       T *const z_re = t.hp_np == 2 ? s2_re : s1_re, *const z_im = t.hp_np == 2 ? s2_im : s1_im;
       // a window that is one of the plan's own tables (pdsp_plan_window_f32) is known by kind: the cosine sum is
       // then evaluated in the first pass instead of being read back (4 more bytes per sample).
       // first = tile_pass_kernel's IN: 3 rect, 4 window table, 5 / 6 fused two- / three-term window
-      int first = window ? 4 : 3;
+      const WindowKind wk = window_kind(t, window, t.hp_win && g_fused_window);
+      int first = window && wk.kind != PDSP_WIN_RECT ? 4 : 3;  // createWindow("rect") is all ones
       pdsp::TileGeom fw{};
-      int kind = -1;
-      for (int k = 0; k < 4; ++k)
-        if (window && window == t.win[k]) kind = k;
-      if (kind == PDSP_WIN_RECT) first = 3;  // createWindow("rect") is all ones
-      if (t.hp_win && g_fused_window && kind > PDSP_WIN_RECT) {
+      if (wk.terms) {
         fw.wa = t.hp_win, fw.wb = fw.wa + 2 * t.hp_win_a, fw.wstep = fw.wb + 2 * 512, fw.we = fw.wstep + 2 * 8;
-        if (kind == PDSP_WIN_HANN) first = 5, fw.k0 = 0.5f, fw.k1 = -0.5f;
-        else if (kind == PDSP_WIN_HAMMING) first = 5, fw.k0 = 0.54f, fw.k1 = -0.46f;
-        else if (kind == PDSP_WIN_BLACKMAN) first = 6, fw.k0 = 0.42f - 0.08f, fw.k1 = -0.5f, fw.k2 = 2 * 0.08f;
+        first = wk.terms == 2 ? 5 : 6, fw.k0 = wk.k0, fw.k1 = wk.k1, fw.k2 = wk.k2;
       }
       if (plan->log2n == 15 && t.tws4 && t.tw12 && g_split16k) {
         // N = 32768: the 16384-point transform is one pass of fft_split4_kernel (14 bytes per sample in all)
         const pdsp::StoreComplex<T> st{z_re, z_im, m, T(1)};
-#define PDSP_SPLIT4_PACKED(W)                                                                                         \
-  hipLaunchKernelGGL((pdsp::fft_split4_kernel<T, 12, pdsp::LoadPackedFrames<T, W>, pdsp::StoreComplex<T>>),           \
-                     dim3((unsigned)batch), dim3(256), 0, stream,                                                     \
-                     pdsp::LoadPackedFrames<T, W>{frames, window, frame_stride, fw.wb, fw.we + 2 * 8, fw.we, fw.k0,   \
-                                                  fw.k1, fw.k2},                                                      \
-                     st, t.tw12, t.tws4, batch)
-        switch (first) {
-          case 3: PDSP_SPLIT4_PACKED(0); break;
-          case 4: PDSP_SPLIT4_PACKED(1); break;
-          case 5: PDSP_SPLIT4_PACKED(2); break;
-          default: PDSP_SPLIT4_PACKED(3); break;
-        }
-#undef PDSP_SPLIT4_PACKED
+        with_int<0, 3>(first - 3, false, [&](auto W) {  // LoadPackedFrames' window mode: first - 3
+          using LD = pdsp::LoadPackedFrames<T, W>;
+          hipLaunchKernelGGL((pdsp::fft_split4_kernel<T, 12, LD, pdsp::StoreComplex<T>>), dim3((unsigned)batch),
+                             dim3(256), 0, stream,
+                             LD{frames, window, frame_stride, fw.wb, fw.we + 2 * 8, fw.we, fw.k0, fw.k1, fw.k2}, st,
+                             t.tw12, t.tws4, batch);
+          return true;
+        });
         PDSP_HIP_TRY(hipGetLastError());
       } else if (plan->log2n == 16 && g_twopass == 1 && t.tws4 && t.tw12) {
         // N = 65536: the 32768-point transform in ONE pass by two sibling workgroups per frame that share an XCD's
         // L2 (fft_paired_kernel, packed loader): 14 bytes per sample in all, where the two tile passes move 22
         const long long blocks = ((batch + 7) / 8) * 8 * 2;
-        if (blocks > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+        if (int rc = check_grid(blocks, batch)) return rc;
         const pdsp::PairedPacked pk{frame_stride, fw.wb, fw.we + 2 * 8, fw.we, fw.k0, fw.k1, fw.k2};
         const pdsp::cx<T> *twa = reinterpret_cast<const pdsp::cx<T> *>(t.twa);
         const pdsp::cx<T> *twb = reinterpret_cast<const pdsp::cx<T> *>(t.twb);
-#define PDSP_PAIRED_PACKED(PK)                                                                                       \
-  hipLaunchKernelGGL((pdsp::fft_paired_kernel<T, 1, false, PK>), dim3((unsigned)blocks), dim3(256), 0, stream, frames,   \
-                     first == 4 ? window : (const T *)nullptr, z_re, z_im, t.tw12, t.tws4, twa, twb, T(1), batch, pk)
-        switch (first) {
-          case 3: PDSP_PAIRED_PACKED(1); break;
-          case 4: PDSP_PAIRED_PACKED(2); break;
-          case 5: PDSP_PAIRED_PACKED(3); break;
-          default: PDSP_PAIRED_PACKED(4); break;
-        }
-#undef PDSP_PAIRED_PACKED
+        with_int<1, 4>(first - 2, false, [&](auto PK) {  // fft_paired_kernel's packed loader: first - 2
+          hipLaunchKernelGGL((pdsp::fft_paired_kernel<T, 1, false, PK>), dim3((unsigned)blocks), dim3(256), 0, stream,
+                             frames, first == 4 ? window : (const T *)nullptr, z_re, z_im, t.tw12, t.tws4, twa, twb, T(1),
+                             batch, pk);
+          return true;
+        });
         PDSP_HIP_TRY(hipGetLastError());
       } else {
         if (int rc = tilepass_chain<T>(t, m, t.hp_np, t.hp_l, t.hp_tw, 1u, first, batch, frames, first == 4 ? window : nullptr,
@@ -760,7 +693,7 @@ int spectrum_impl(const pdsp_plan *plan, long long batch, const T *frames, long 
           return rc;
       }
       const long long chunks = m / 2048;  // 256 lanes of four pairs each
-      if (batch * chunks > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+      if (int rc = check_grid(batch * chunks, batch)) return rc;
       hipLaunchKernelGGL((pdsp::split_amp_rows_kernel<T>), dim3((unsigned)(batch * chunks)), dim3(256), 0, stream,
                          (const T *)z_re, (const T *)z_im, amp, ph, reinterpret_cast<const pdsp::cx<T> *>(t.twa),
                          reinterpret_cast<const pdsp::cx<T> *>(t.twb), (int)m, bins, s_edge, s_mid, batch);
@@ -779,12 +712,10 @@ int spectrum_impl(const pdsp_plan *plan, long long batch, const T *frames, long 
     const bool big = t.log2n1 > pdsp::kMaxLog2N1;  // general path: two scratch pairs
     T *amp = amp_out, *ph = phase_out;
     const size_t plane = (size_t)batch * (size_t)n, rows = (size_t)batch * bins, planes = big ? 4 : 2;
-    const size_t extra = (peaks_out && !amp ? rows : 0) + (peaks_out && !ph ? rows : 0);
     StreamScratch mem(stream);
-    PDSP_HIP_TRY(mem.alloc((planes * plane + extra) * sizeof(T)));
+    PDSP_HIP_TRY(mem.alloc((planes * plane + peak_rows_extra(peaks_out, amp, ph, rows)) * sizeof(T)));
     T *const scratch = (T *)mem.p;
-    if (peaks_out && !amp) amp = scratch + planes * plane;
-    if (peaks_out && !ph) ph = scratch + planes * plane + (amp_out ? 0 : rows);
+    place_peak_rows(peaks_out, amp, ph, scratch + planes * plane, rows);
     const int nyq = (sides == PDSP_SIDES_ONE) ? (int)(n / 2) : -1;
     int rc;
     if (big) {
@@ -800,35 +731,26 @@ int spectrum_impl(const pdsp_plan *plan, long long batch, const T *frames, long 
       rc = fail(PDSP_ERR_DEVICE, "peak kernel launch failed");
     return rc;
   }
-  constexpr uintptr_t kPairMask = 2 * sizeof(T) - 1;  // alignment of one (re, im) pair
   if (t.tw_half) {
     // packed-real path (N >= 64): N/2-point complex transform + Hermitian split (+ findPeak) fused with the store.
     // fast variant: whole pair-aligned frames (and window), one-sided, no phase rows (config 4's shape); the
     // general variant takes any frame length, stride and alignment of frames and window
-    const bool fast = ((uintptr_t)frames & kPairMask) == 0 && (frame_stride & 1) == 0 && used == n &&
-                      sides == PDSP_SIDES_ONE && phase_out == nullptr && ((uintptr_t)window & kPairMask) == 0;
+    const bool fast = aligned(2 * sizeof(T), frames, window) && (frame_stride & 1) == 0 && used == n &&
+                      sides == PDSP_SIDES_ONE && phase_out == nullptr;  // aligned to one (re, im) pair
     // 64 <= N <= 512, amplitude only: contiguous frames staged in / amplitude rows staged out through LDS
     // (f32 only: in f64 the two LDS regions take 102 KB, one workgroup per CU, and measure slower than the direct kernel)
     if (sizeof(T) == 4 && fast && !peaks_out && !peak_idx_out && plan->log2n >= 6 && plan->log2n <= 9 && g_staged_small &&
-        frame_stride == n &&
-        ((uintptr_t)frames & (4 * sizeof(T) - 1)) == 0 && ((uintptr_t)window & (4 * sizeof(T) - 1)) == 0) {
+        frame_stride == n && aligned(4 * sizeof(T), frames, window)) {
       const long long blocks = (batch * (n / 2) + 4095) / 4096;
-#define PDSP_SSTAGED(LM)                                                                                            \
-  do {                                                                                                              \
-    if (window)                                                                                                     \
-      hipLaunchKernelGGL((pdsp::spectrum_staged_kernel<T, LM, true>), dim3((unsigned)blocks), dim3(256), 0, stream,  \
-                         frames, window, t.tw_half, t.twr, amp_out, s_edge, s_mid, batch);                          \
-    else                                                                                                            \
-      hipLaunchKernelGGL((pdsp::spectrum_staged_kernel<T, LM, false>), dim3((unsigned)blocks), dim3(256), 0, stream, \
-                         frames, window, t.tw_half, t.twr, amp_out, s_edge, s_mid, batch);                          \
-  } while (0)
-      switch (plan->log2n - 1) {
-        case 5: PDSP_SSTAGED(5); break;
-        case 6: PDSP_SSTAGED(6); break;
-        case 7: PDSP_SSTAGED(7); break;
-        default: PDSP_SSTAGED(8); break;
-      }
-#undef PDSP_SSTAGED
+      with_int<5, 8>(plan->log2n - 1, false, [&](auto LM) {
+        auto go = [&](auto win_c) {
+          hipLaunchKernelGGL((pdsp::spectrum_staged_kernel<T, LM, win_c>), dim3((unsigned)blocks), dim3(256), 0, stream,
+                             frames, window, t.tw_half, t.twr, amp_out, s_edge, s_mid, batch);
+        };
+        if (window) go(std::true_type{});
+        else go(std::false_type{});
+        return true;
+      });
       PDSP_HIP_TRY(hipGetLastError());
       return PDSP_OK;
     }
@@ -839,20 +761,15 @@ int spectrum_impl(const pdsp_plan *plan, long long batch, const T *frames, long 
     pdsp::WinFused wf{nullptr, nullptr, 0.f, 0.f, 0.f, 1.f};
     int wmode = window ? 1 : 0;
     if constexpr (sizeof(T) == 4) {
-      int kind = -1;  // -1: caller's table
-      for (int k = 0; k < 4; ++k)
-        if (window && window == t.win[k]) kind = k;
-      if (kind == PDSP_WIN_RECT) wmode = 0;  // createWindow("rect") is all ones
-      if (t.wf_base && g_fused_window && fast) {
-        wf.base = t.wf_base, wf.step = t.wf_step;
-        if (kind == PDSP_WIN_HANN) wmode = 2, wf.k0 = 0.5f, wf.k1 = -0.5f;
-        else if (kind == PDSP_WIN_HAMMING) wmode = 2, wf.k0 = 0.54f, wf.k1 = -0.46f;
-        else if (kind == PDSP_WIN_BLACKMAN) wmode = 3, wf.k0 = 0.42f - 0.08f, wf.k1 = -0.5f, wf.k2 = 2 * 0.08f;
-        if (wmode >= 2) {  // the kernels take the fused coefficients pre-scaled by s_mid / 2 (a power of two: exact)
-          const float g = 0.5f * (float)s_mid;
-          wf.k0 *= g, wf.k1 *= g, wf.k2 *= g;
-          wf.edge_ratio = (float)(s_edge / s_mid);
-        }
+      const bool fuse = t.wf_base && g_fused_window && fast;
+      const WindowKind wk = window_kind(t, window, fuse);
+      if (wk.kind == PDSP_WIN_RECT) wmode = 0;  // createWindow("rect") is all ones
+      if (fuse) wf.base = t.wf_base, wf.step = t.wf_step;
+      if (wk.terms) {  // the kernels take the fused coefficients pre-scaled by s_mid / 2 (a power of two: exact)
+        const float g = 0.5f * (float)s_mid;
+        wmode = wk.terms;
+        wf.k0 = wk.k0 * g, wf.k1 = wk.k1 * g, wf.k2 = wk.k2 * g;
+        wf.edge_ratio = (float)(s_edge / s_mid);
       }
     }
     if constexpr (sizeof(T) == 4) {
@@ -863,23 +780,16 @@ int spectrum_impl(const pdsp_plan *plan, long long batch, const T *frames, long 
       // read back, 64 KB per frame, from L2.  Any other window pointer is read as a table.
       if (fast && plan->log2n == 14 && g_split16k && t.wf_base) {
         pdsp::PeakRec *pk = reinterpret_cast<pdsp::PeakRec *>(peaks_out);
-        const int mode = wmode;
-#define PDSP_DIF(W, P)                                                                                              \
-  hipLaunchKernelGGL((pdsp::spectrum_dif16k_kernel<T, W, P>), dim3((unsigned)batch), dim3(256), 0, stream, frames,  \
-                     window, wf, frame_stride, t.tw12, t.twr, amp_out, s_edge, s_mid, pk, freq_scale, batch)
-#define PDSP_DIF_P(W)    \
-  do {                   \
-    if (pk) PDSP_DIF(W, true); \
-    else PDSP_DIF(W, false);   \
-  } while (0)
-        switch (mode) {
-          case 0: PDSP_DIF_P(0); break;
-          case 1: PDSP_DIF_P(1); break;
-          case 2: PDSP_DIF_P(2); break;
-          default: PDSP_DIF_P(3); break;
-        }
-#undef PDSP_DIF_P
-#undef PDSP_DIF
+        with_int<0, 3>(wmode, false, [&](auto W) {
+          auto go = [&](auto peak_c) {
+            hipLaunchKernelGGL((pdsp::spectrum_dif16k_kernel<T, W, peak_c>), dim3((unsigned)batch), dim3(256), 0, stream,
+                               frames, window, wf, frame_stride, t.tw12, t.twr, amp_out, s_edge, s_mid, pk, freq_scale,
+                               batch);
+          };
+          if (pk) go(std::true_type{});
+          else go(std::false_type{});
+          return true;
+        });
         PDSP_HIP_TRY(hipGetLastError());
         launched = true;  // a requested peak-index array is filled by the common tail below
       }
@@ -893,7 +803,7 @@ int spectrum_impl(const pdsp_plan *plan, long long batch, const T *frames, long 
     // complex kernel on (x, 0) for N < 64 (the sizes without packed-real tables); peaks come from the stored rows
     if (!t.tw || plan->log2n > 5) return fail(PDSP_ERR_UNSUPPORTED_SIZE, "no spectrum tables for size %lld", plan->n);
     if (plan->log2n >= 1 && plan->log2n <= 5 && g_staged_small && used == n && frame_stride == n && amp_out &&
-        !phase_out && !peaks_out && ((uintptr_t)frames & (4 * sizeof(T) - 1)) == 0) {
+        !phase_out && !peaks_out && aligned(4 * sizeof(T), frames)) {
       // 2 <= N <= 32, whole contiguous frames, amplitude only: one thread per frame, chunk staged through LDS
       pdsp::LoadReal<T> ld{frames, n};
       PDSP_HIP_TRY((launch_tiny<T, true>(plan->log2n, ld, window, amp_out, (T *)nullptr, T(1), bins,
@@ -903,15 +813,11 @@ int spectrum_impl(const pdsp_plan *plan, long long batch, const T *frames, long 
       return PDSP_OK;
     }
     T *amp = amp_out, *ph = phase_out;
-    const size_t row_bytes = (size_t)batch * bins * sizeof(T);
-    StreamScratch tmp_amp(stream), tmp_ph(stream);  // peaks-only output: the rows live in scratch
-    if (peaks_out && !amp) {
-      PDSP_HIP_TRY(tmp_amp.alloc(row_bytes));
-      amp = (T *)tmp_amp.p;
-    }
-    if (peaks_out && !ph) {
-      PDSP_HIP_TRY(tmp_ph.alloc(row_bytes));
-      ph = (T *)tmp_ph.p;
+    const size_t rows = (size_t)batch * bins;
+    StreamScratch mem(stream);
+    if (const size_t extra = peak_rows_extra(peaks_out, amp, ph, rows)) {
+      PDSP_HIP_TRY(mem.alloc(extra * sizeof(T)));
+      place_peak_rows(peaks_out, amp, ph, (T *)mem.p, rows);
     }
     pdsp::StoreAmplitude<T> st{amp, ph, bins,
                                // scaleAmplitudeOneSided: `nyquist = size % 2 === 0 ? size/2 : -1`; N = 1 is odd

@@ -106,27 +106,12 @@ template <typename T>
 __device__ __forceinline__ cx<T> conj(const cx<T> a) {
   return cx<T>{a.x, -a.y};
 }
-// a + (-i)*b = (a.re + b.im, a.im - b.re)  and  a + i*b = (a.re - b.im, a.im + b.re).
-// ONE packed instruction each.  hipcc does not fold a per-half negation into v_pk_add_f32's neg_lo / neg_hi (written as
-// plain arithmetic it materialises (-i)*b with a v_xor + v_mov first: 21 % of the N=16384 spectrum kernel's vector
-// instructions were such pairs in round 1), so rounds 1-2 spelled the add in inline asm with op_sel / neg modifiers.
-// Round 3: hipcc DOES fold the half swap of a v_pk_fma_f32 operand into op_sel, and a multiply by (1, -1) is exact, so
-// fma(b.yx, (1, -1), a) is the same value bit for bit, one v_pk_fma_f32 with the constant in an SGPR pair -- and no
-// inline asm: every asm statement is an opaque instruction that hipcc pads with an s_nop against its neighbours
-// (68 of the N=4096 complex kernel's 673 instructions were such pads) and cannot schedule around.
-#ifndef PDSP_CMUL_ONE_ASM
-#define PDSP_CMUL_ONE_ASM 1
-#endif
-#ifndef PDSP_ROT_ASM
-#define PDSP_ROT_ASM 0  /* 1: rounds 1-2's inline-asm v_pk_add_f32 forms (A/B builds) */
-#endif
+// a + (-i)*b = (a.re + b.im, a.im - b.re)  and  a + i*b = (a.re - b.im, a.im + b.re): ONE v_pk_fma_f32 each, since
+// hipcc folds the half swap of fma(b.yx, (1, -1), a) into op_sel (exact).  Plain arithmetic materialises (-i)*b first;
+// the inline-asm v_pk_add_f32 of rounds 1-2 cost an s_nop pad per statement (68 of 673 instructions at N=4096).
 template <typename T>
 __device__ __forceinline__ cx<T> add_mul_neg_i(const cx<T> a, const cx<T> b) {
-  if constexpr (std::is_same_v<T, float> && PDSP_ROT_ASM) {
-    cx<float> r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-  } else if constexpr (std::is_same_v<T, float>) {
+  if constexpr (std::is_same_v<T, float>) {
     return __builtin_elementwise_fma(__builtin_shufflevector(b, b, 1, 0), cx<float>{1.0f, -1.0f}, a);
   } else {
     return cx<T>{a.x + b.y, a.y - b.x};
@@ -134,11 +119,7 @@ __device__ __forceinline__ cx<T> add_mul_neg_i(const cx<T> a, const cx<T> b) {
 }
 template <typename T>
 __device__ __forceinline__ cx<T> add_mul_pos_i(const cx<T> a, const cx<T> b) {
-  if constexpr (std::is_same_v<T, float> && PDSP_ROT_ASM) {
-    cx<float> r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-  } else if constexpr (std::is_same_v<T, float>) {
+  if constexpr (std::is_same_v<T, float>) {
     return __builtin_elementwise_fma(__builtin_shufflevector(b, b, 1, 0), cx<float>{-1.0f, 1.0f}, a);
   } else {
     return cx<T>{a.x - b.y, a.y + b.x};
@@ -149,21 +130,14 @@ __device__ __forceinline__ cx<T> add_mul_pos_i(const cx<T> a, const cx<T> b) {
 template <typename T>
 __device__ __forceinline__ cx<T> cmul(const cx<T> a, const cx<T> w) {
   if constexpr (std::is_same_v<T, float>) {
-#if PDSP_CMUL_ONE_ASM
     // both instructions in ONE statement (the product accumulates in the result register): half the asm boundaries
-    // for hipcc to pad, one register less
+    // for hipcc to pad, one register less than two statements
     cx<float> r;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]\n\t"
         "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]"
         : "=&v"(r)
         : "v"(a), "v"(w));
     return r;
-#else
-    cx<float> t, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(t) : "v"(a), "v"(w));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]" : "=v"(r) : "v"(a), "v"(w), "v"(t));
-    return r;
-#endif
   } else {
     return a.xx * w + a.yy * cx<T>{-w.y, w.x};
   }
@@ -322,22 +296,11 @@ __device__ __forceinline__ long long uniform_row(long long row) {
   else return row;
 }
 
-// Order of a kernel's first loads: 1 = the L2-resident tables a thread needs (twiddle bases, split
-// twiddles, window values) are requested BEFORE its streamed row (HBM).  The memory counter retires in
-// issue order and the vector-memory pipeline is a queue: table loads issued behind the row loads sit
-// behind 16-64 KB of streaming requests and their data is not usable until every older HBM load is back.
-// Round 1 issued them "right behind the row loads".  Measured A/B (tools/kbench, tools/sweep.py with
-// PDSP_LIB_PATH): the fused spectrum kernels, which carry a window's worth of table loads, gain
-// (N=16384 decimation-in-time kernel 5.07-5.12 -> 5.40 TB/s; packed kernel N=1024 / 2048 / 4096 / 8192
-// +3 / +4 / +1 / +1 %), the N=16384 complex kernel gains +2...7 %; the plain transforms, whose only
-// tables are 12-14 twiddle bases, LOSE 1 % (complex) to 3.5 % (real input) -- there the bases stay
-// behind the row loads (PDSP_TABLES_FIRST_C2C 0).  0 / 1 are compile-time A/B switches.
-#ifndef PDSP_TABLES_FIRST
-#define PDSP_TABLES_FIRST 1      /* spectrum_packed_kernel, fft_split4_kernel, fft_split2_kernel */
-#endif
-#ifndef PDSP_TABLES_FIRST_C2C
-#define PDSP_TABLES_FIRST_C2C 0  /* fft_stockham_kernel */
-#endif
+// Order of a kernel's first loads.  The memory counter retires in issue order, so table loads issued behind a row's
+// HBM loads wait for all of them.  The spectrum and split kernels request their L2-resident tables (twiddle bases,
+// split twiddles, window values) BEFORE the streamed row: packed kernel +1 ... +4 %, N=16384 spectrum 5.07 -> 5.40
+// TB/s, N=16384 complex +2 ... 7 %.  The plain transforms (fft_stockham_kernel, fft_real_kernel), whose only tables
+// are 12-14 twiddle bases, lose 1-3.5 % that way and load them behind the row ("Tables first").
 __device__ __forceinline__ void load_order_fence() { __builtin_amdgcn_sched_barrier(0); }
 
 // Streamed rows are touched exactly once: non-temporal loads/stores keep them from
@@ -347,17 +310,9 @@ template <typename T>
 __device__ __forceinline__ T ld_stream(const T *p) { return __builtin_nontemporal_load(p); }
 template <typename T>
 __device__ __forceinline__ void st_stream(T v, T *p) { __builtin_nontemporal_store(v, p); }
-// Amplitude / phase rows are N/2+1 floats long, so a wave's 256-byte store straddles
-// cache lines that the neighbouring waves complete: plain stores let L2 combine them
+// Amplitude / phase rows of dword stores take plain stores: they are N/2+1 floats long, so a wave's 256-byte store
+// straddles cache lines that the neighbouring waves complete, and L2 combines plain stores
 // (PMC: non-temporal stores wrote 13 % more than the algorithmic bytes here).
-#ifndef PDSP_AMP_STORE_NT
-#define PDSP_AMP_STORE_NT 0
-#endif
-template <typename T>
-__device__ __forceinline__ void st_rowtail(T v, T *p) {
-  if constexpr (PDSP_AMP_STORE_NT) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
 
 // |z| for the fused amplitude stores: one v_sqrt_f32 (1 ulp) instead of the ~10-instruction
 // correctly rounded sequence -- 17 of them per thread sit in the VALU-bound epilogue of the
@@ -774,18 +729,10 @@ fft_stockham_kernel(const LD ld, const ST st, const typename vec2<T>::type *__re
   cx<T> *const lrow = lds + (NP > 1 ? rloc * TR::LROW : 0);
 
   cx<T> x[E];
-#ifndef PDSP_C2C_TABLE_TWIDDLES
   constexpr bool kRegTw = (TP >= 16 && NP > 1);  // twiddle bases in registers, fetched with the row loads
-#else
-  constexpr bool kRegTw = false;
-#endif
   std::conditional_t<kRegTw, RegTwiddles<T, LOG2N>, TableTwiddles<T, LOG2N>> twf;
-  if constexpr (kRegTw && PDSP_TABLES_FIRST_C2C) {
-    twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
-    load_order_fence();
-  }
   static_for<E>([&](auto q) { x[q] = ld(row, TP * q, tid); });
-  if constexpr (kRegTw && !PDSP_TABLES_FIRST_C2C) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
+  if constexpr (kRegTw) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);  // behind the row loads
   if constexpr (!kRegTw) twf.tw = reinterpret_cast<const cx<T> *>(tw);
   fft_passes<T, LOG2N, false>(x, lrow, twf, tid);
   if (live) {
@@ -1002,14 +949,11 @@ spectrum_packed_kernel(const T *__restrict__ frames, const T *__restrict__ win, 
   static_assert(LOG2M >= 5, "packed path needs TP >= 2");
   constexpr bool HAS_WIN = WIN == 1;
   static_assert(WIN <= 1 || (FAST && sizeof(T) == 4 && LOG2E == 4), "fused windows: whole f32 frames");
-#ifndef PDSP_PACKED_ADJ
-#define PDSP_PACKED_ADJ 1  /* 0: round-1 split (bins tid + TP*q, dword stores in two directions): A/B builds */
-#endif
   // adjacent-bin 8-byte non-temporal stores pay when a wave's stores cover whole cache lines of one row
   // (TP >= 32: N >= 1024).  Below that a wave spans many short rows and each lane's 8 / 16 bytes would be
   // a partial-line streaming write: measured 1.8 -> 0.8 TB/s at N = 64 (f32, staged path off) and
   // 36 -> 22 % in f64 -- those sizes keep round 1's split (dword stores that L2 merges).
-  constexpr bool kAdj = FAST && LOG2E == 4 && TP >= 32 && PDSP_PACKED_ADJ;
+  constexpr bool kAdj = FAST && LOG2E == 4 && TP >= 32;
   typedef T V4 __attribute__((ext_vector_type(4)));
 
   __shared__ cx<T> lds[TR::LDS_ELEMS];
@@ -1024,27 +968,25 @@ spectrum_packed_kernel(const T *__restrict__ frames, const T *__restrict__ win, 
   // buildFrame + applyWindow (spectrum.ts:36-43, :116-119) on load; m = tid + TP*q
   const T *const xrow = frames + (size_t)row * (size_t)stride;
   cx<T> x[E];
-  // tables first (PDSP_TABLES_FIRST): twiddle bases, the split twiddle, the thread's window values
+  // tables first: twiddle bases, the split twiddle, the thread's window values
   constexpr bool kRegTw = (LOG2E == 4 && TP >= 16);
   std::conditional_t<kRegTw, RegTwiddles<T, LOG2M, LOG2E>, TableTwiddles<T, LOG2M, LOG2E>> twf;
-  cx<T> twk0;
+  cx<T> twk0;  // W_N^tid: the Hermitian split needs W_N^(tid + TP*q) = twk0 * W32^q (N = 32*TP)
   V4 tb = V4{T(0), T(0), T(0), T(0)};  // kAdj: (W_N^(2 tid), W_N^(2 tid + 1)), the split's two bases
   V4 wb4 = V4{T(0), T(0), T(0), T(0)};  // fused window: the thread's base (cos, sin) pairs
-  cx<T> wv[(HAS_WIN && PDSP_TABLES_FIRST) ? E : 1];
-  if constexpr (PDSP_TABLES_FIRST) {
-    if constexpr (kRegTw) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
-    if constexpr (kAdj) tb = reinterpret_cast<const V4 *>(twr)[(unsigned)tid];
-    else twk0 = reinterpret_cast<const cx<T> *>(twr)[(unsigned)tid];
-    if constexpr (WIN >= 2) wb4 = reinterpret_cast<const V4 *>(wf.base)[(unsigned)tid];
-    if constexpr (HAS_WIN && FAST) {
-      const cx<T> *const w2 = reinterpret_cast<const cx<T> *>(win);
-      static_for<E>([&](auto q) { wv[q] = (w2 + TP * q)[(unsigned)tid]; });
-    } else if constexpr (HAS_WIN) {
-      // the general variant takes a window at ANY alignment (a view one value into a tensor): two scalar loads
-      static_for<E>([&](auto q) { wv[q] = cx<T>{(win + 2 * TP * q)[2 * (unsigned)tid], (win + 2 * TP * q + 1)[2 * (unsigned)tid]}; });
-    }
-    load_order_fence();
+  cx<T> wv[HAS_WIN ? E : 1];
+  if constexpr (kRegTw) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
+  if constexpr (kAdj) tb = reinterpret_cast<const V4 *>(twr)[(unsigned)tid];
+  else twk0 = reinterpret_cast<const cx<T> *>(twr)[(unsigned)tid];
+  if constexpr (WIN >= 2) wb4 = reinterpret_cast<const V4 *>(wf.base)[(unsigned)tid];
+  if constexpr (HAS_WIN && FAST) {
+    const cx<T> *const w2 = reinterpret_cast<const cx<T> *>(win);
+    static_for<E>([&](auto q) { wv[q] = (w2 + TP * q)[(unsigned)tid]; });
+  } else if constexpr (HAS_WIN) {
+    // the general variant takes a window at ANY alignment (a view one value into a tensor): two scalar loads
+    static_for<E>([&](auto q) { wv[q] = cx<T>{(win + 2 * TP * q)[2 * (unsigned)tid], (win + 2 * TP * q + 1)[2 * (unsigned)tid]}; });
   }
+  load_order_fence();
   // (Buffer-form addressing -- one descriptor per row, scalar q offsets -- gains 4-5 % on the N = 16384
   // kernel, where it removes ~100 address instructions; here, A/B with tools/sweep.py, it measured +-0 at
   // N = 2048 / 8192 and -2 % at 4096, so the flat form stays.)
@@ -1063,38 +1005,23 @@ spectrum_packed_kernel(const T *__restrict__ frames, const T *__restrict__ win, 
   }
   PDSP_STAMP_INIT();
   if constexpr (!kRegTw) twf.tw = reinterpret_cast<const cx<T> *>(tw);
-  if constexpr (PDSP_TABLES_FIRST) {
-    load_order_fence();
-    if constexpr (HAS_WIN) static_for<E>([&](auto q) { x[q] = x[q] * wv[q]; });
-    if constexpr (WIN >= 2) {
-      static_assert(WIN < 2 || kAdj, "the fused windows' pre-scaled frames are split by the adjacent-bin code");
-      const cx<T> cb{wb4.x, wb4.z}, sb{wb4.y, wb4.w};  // (e = 0, e = 1)
-      const T k0 = wf.k0, k1 = wf.k1, k2 = wf.k2;        // pre-scaled by s_mid / 2 on the host (WinFused)
-      const cx<T> kc = cb * k1, ks = sb * k1;             // two-term form: w = k0 + kc cos_q - ks sin_q
-      static_for<E>([&](auto qc) {
-        constexpr int q = qc;
-        const T cq = wf.step[2 * q], sq = wf.step[2 * q + 1];  // wave-uniform: scalar loads
-        if constexpr (WIN == 3) {
-          const cx<T> c = cb * cq - sb * sq;                   // cos(f n), n = 2 (tid + TP q) + e
-          x[q] = x[q] * (k0 + c * (k1 + k2 * c));
-        } else {
-          x[q] = x[q] * ((k0 + kc * cq) - ks * sq);
-        }
-      });
-    }
-  } else {
-    // round-1 order: twiddle bases right behind the frame loads, consumed passes later
-    if constexpr (kRegTw) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
-    // W_N^tid: the Hermitian split needs W_N^(tid + TP*q) = twk0 * W32^q (N = 32*TP)
-    if constexpr (kAdj) tb = reinterpret_cast<const V4 *>(twr)[(unsigned)tid];
-    else twk0 = reinterpret_cast<const cx<T> *>(twr)[(unsigned)tid];
-    static_assert(WIN <= 1 || PDSP_TABLES_FIRST, "fused windows are written for the tables-first order");
-    if constexpr (HAS_WIN && FAST) {
-      const cx<T> *const w2 = reinterpret_cast<const cx<T> *>(win);
-      static_for<E>([&](auto q) { x[q] = x[q] * (w2 + TP * q)[(unsigned)tid]; });
-    } else if constexpr (HAS_WIN) {
-      static_for<E>([&](auto q) { x[q] = x[q] * cx<T>{(win + 2 * TP * q)[2 * (unsigned)tid], (win + 2 * TP * q + 1)[2 * (unsigned)tid]}; });
-    }
+  load_order_fence();
+  if constexpr (HAS_WIN) static_for<E>([&](auto q) { x[q] = x[q] * wv[q]; });
+  if constexpr (WIN >= 2) {
+    static_assert(WIN < 2 || kAdj, "the fused windows' pre-scaled frames are split by the adjacent-bin code");
+    const cx<T> cb{wb4.x, wb4.z}, sb{wb4.y, wb4.w};  // (e = 0, e = 1)
+    const T k0 = wf.k0, k1 = wf.k1, k2 = wf.k2;        // pre-scaled by s_mid / 2 on the host (WinFused)
+    const cx<T> kc = cb * k1, ks = sb * k1;             // two-term form: w = k0 + kc cos_q - ks sin_q
+    static_for<E>([&](auto qc) {
+      constexpr int q = qc;
+      const T cq = wf.step[2 * q], sq = wf.step[2 * q + 1];  // wave-uniform: scalar loads
+      if constexpr (WIN == 3) {
+        const cx<T> c = cb * cq - sb * sq;                   // cos(f n), n = 2 (tid + TP q) + e
+        x[q] = x[q] * (k0 + c * (k1 + k2 * c));
+      } else {
+        x[q] = x[q] * ((k0 + kc * cq) - ks * sq);
+      }
+    });
   }
   // The adjacent-bin split takes a frame PRE-SCALED by g = s_mid / 2 (a power of two: exact) and multiplies by
   // nothing: the fused windows carry g in their coefficients (WinFused); the rect and table variants multiply here --
@@ -1168,7 +1095,7 @@ spectrum_packed_kernel(const T *__restrict__ frames, const T *__restrict__ win, 
       const cx<T> xm = conj(lrow[lds_pad(M / 2)]) * T(2);  // the pre-scaled frame carries s_mid / 2; one value, not a sum
       const T mm = mag(xm);
       if constexpr (PEAK) best.consider(mm, M / 2, xm);
-      if (store_amp) st_rowtail(mm, arow + (unsigned)(M / 2));
+      if (store_amp) arow[(unsigned)(M / 2)] = mm;
     }
   }
   // pairs k = tid + TP*q, q < E/2 (k < M/2); k = M/2 is one more pair for tid == 0.
@@ -1211,19 +1138,19 @@ spectrum_packed_kernel(const T *__restrict__ frames, const T *__restrict__ win, 
         if (k2 != k) best.consider(mb, k2, xb);
       }
       if (store_amp) {
-        st_rowtail(ma, arow + (unsigned)k);
-        if (k2 != k) st_rowtail(mb, arow + (unsigned)k2);
+        arow[(unsigned)k] = ma;
+        if (k2 != k) arow[(unsigned)k2] = mb;
         if constexpr (!FAST) {
           if (two_sided && k != 0) {  // X[N-k] = conj X[k]
-            st_rowtail(ma, arow + (unsigned)(2 * M - k));
-            if (k2 != k) st_rowtail(mb, arow + (unsigned)(2 * M - k2));
+            arow[(unsigned)(2 * M - k)] = ma;
+            if (k2 != k) arow[(unsigned)(2 * M - k2)] = mb;
           }
           if (prow) {
-            st_rowtail(T(atan2(xa.y, xa.x)), prow + (unsigned)k);
-            if (k2 != k) st_rowtail(T(atan2(xb.y, xb.x)), prow + (unsigned)k2);
+            prow[(unsigned)k] = T(atan2(xa.y, xa.x));
+            if (k2 != k) prow[(unsigned)k2] = T(atan2(xb.y, xb.x));
             if (two_sided && k != 0) {
-              st_rowtail(T(atan2(-xa.y, xa.x)), prow + (unsigned)(2 * M - k));
-              if (k2 != k) st_rowtail(T(atan2(-xb.y, xb.x)), prow + (unsigned)(2 * M - k2));
+              prow[(unsigned)(2 * M - k)] = T(atan2(-xa.y, xa.x));
+              if (k2 != k) prow[(unsigned)(2 * M - k2)] = T(atan2(-xb.y, xb.x));
             }
           }
         }
@@ -1314,18 +1241,12 @@ fft_real_kernel(const T *__restrict__ xin, T *__restrict__ ore, T *__restrict__ 
 
   RegTwiddles<T, LOG2M, LOG2E> twf;
   cx<T> twk0;
-  if constexpr (PDSP_TABLES_FIRST_C2C) {
-    twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
-    twk0 = reinterpret_cast<const cx<T> *>(twr)[(unsigned)tid];
-    load_order_fence();
-  }
   const cx<T> *const x2 = reinterpret_cast<const cx<T> *>(xin + (size_t)row * (size_t)(2 * M));
   cx<T> x[E];
   static_for<E>([&](auto q) { x[q] = ld_stream(x2 + TP * q + (unsigned)tid); });
-  if constexpr (!PDSP_TABLES_FIRST_C2C) {
-    twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
-    twk0 = reinterpret_cast<const cx<T> *>(twr)[(unsigned)tid];  // W_N^tid; W_N^(tid + TP q) = twk0 * W_32^q (N = 32 TP)
-  }
+  // the tables behind the row loads (load_order_fence's header)
+  twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
+  twk0 = reinterpret_cast<const cx<T> *>(twr)[(unsigned)tid];  // W_N^tid; W_N^(tid + TP q) = twk0 * W_32^q (N = 32 TP)
 
   fft_passes<T, LOG2M, true, LOG2E>(x, lrow, twf, tid);  // Z in LDS, natural order
   __syncthreads();
@@ -1669,11 +1590,9 @@ fft_split4_kernel(const LD ld, const ST st, const typename vec2<T>::type *__rest
   RegTwiddles<T, LOG2S> twf;
   const cx<T> *const twn = reinterpret_cast<const cx<T> *>(tws);
   cx<T> w1, w2, w3;
-  if constexpr (PDSP_TABLES_FIRST) {
-    twf.load(reinterpret_cast<const cx<T> *>(tw12), tid);
-    w1 = twn[(unsigned)tid], w2 = twn[(unsigned)(2 * tid)], w3 = twn[(unsigned)(3 * tid)];
-    load_order_fence();
-  }
+  twf.load(reinterpret_cast<const cx<T> *>(tw12), tid);  // tables first (load_order_fence's header)
+  w1 = twn[(unsigned)tid], w2 = twn[(unsigned)(2 * tid)], w3 = twn[(unsigned)(3 * tid)];
+  load_order_fence();
   if constexpr (LD::kPacked) {
     // points 4m .. 4m+3 = samples 8m .. 8m+7 of the frame: two 16-byte loads (+ two of the window table)
     const V4 *const f4 = reinterpret_cast<const V4 *>(ld.x + (size_t)row * (size_t)ld.stride);
@@ -1724,10 +1643,6 @@ fft_split4_kernel(const LD ld, const ST st, const typename vec2<T>::type *__rest
       c[q] = cx<T>{r.z, T(0)};
       d[q] = cx<T>{r.w, T(0)};
     });
-  }
-  if constexpr (!PDSP_TABLES_FIRST) {
-    twf.load(reinterpret_cast<const cx<T> *>(tw12), tid);
-    w1 = twn[(unsigned)tid], w2 = twn[(unsigned)(2 * tid)], w3 = twn[(unsigned)(3 * tid)];
   }
 
   fft_passes<T, LOG2S, false>(a, lds, twf, tid);  // a[e] = F0[tid + TP*e]
@@ -1947,11 +1862,9 @@ fft_split2_kernel(const LD ld, const ST st, const typename vec2<T>::type *__rest
   constexpr bool kTableTw = sizeof(T) == 8 && LD::kHasIm;
   std::conditional_t<kTableTw, TableTwiddles<T, 12>, RegTwiddles<T, 12>> twf;
   cx<T> w1;
-  if constexpr (PDSP_TABLES_FIRST) {
-    if constexpr (!kTableTw) twf.load(reinterpret_cast<const cx<T> *>(tw12), tid);
-    w1 = reinterpret_cast<const cx<T> *>(tws)[(unsigned)tid];
-    load_order_fence();
-  }
+  if constexpr (!kTableTw) twf.load(reinterpret_cast<const cx<T> *>(tw12), tid);  // tables first
+  w1 = reinterpret_cast<const cx<T> *>(tws)[(unsigned)tid];
+  load_order_fence();
   if constexpr (LD::kHasIm) {
     const cx<T> *const i2 = reinterpret_cast<const cx<T> *>(ld.plane_im() + (size_t)row * N);
     static_for<E>([&](auto q) {
@@ -1968,10 +1881,6 @@ fft_split2_kernel(const LD ld, const ST st, const typename vec2<T>::type *__rest
     });
   }
   if constexpr (kTableTw) twf.tw = reinterpret_cast<const cx<T> *>(tw12);
-  if constexpr (!PDSP_TABLES_FIRST) {
-    if constexpr (!kTableTw) twf.load(reinterpret_cast<const cx<T> *>(tw12), tid);
-    w1 = reinterpret_cast<const cx<T> *>(tws)[(unsigned)tid];
-  }
 
   fft_passes<T, 12, false>(a, lds, twf, tid);  // a[e] = E[tid + 256e]
   __syncthreads();                            // the buffer is reused by the second transform
@@ -2027,7 +1936,7 @@ spectrum_dif16k_kernel(const T *__restrict__ frames, const T *__restrict__ win, 
                        const typename vec2<T>::type *__restrict__ twr, T *__restrict__ amp, const T s_edge,
                        const T s_mid, PeakRec *__restrict__ peaks, const T freq_scale, const long long batch) {
   constexpr bool HAS_WIN = WIN == 1;
-  static_assert(WIN <= 1 || sizeof(T) == 4, "the fused window is the f32 path's (f64 keeps the f64-built table)");
+  static_assert(sizeof(T) == 4, "f32 only: f64 frames of N = 16384 run on spectrum_packed_kernel<double, 13>");
   using TR = FftTraits<12>;
   constexpr int E = 16, TP = 256, H = 4096, M = 8192, Q = 2048;
   typedef T V4 __attribute__((ext_vector_type(4)));
@@ -2038,7 +1947,7 @@ spectrum_dif16k_kernel(const T *__restrict__ frames, const T *__restrict__ win, 
   if (row >= batch) return;
   const cx<T> *const tw = reinterpret_cast<const cx<T> *>(tw12);
 
-  // tables first (PDSP_TABLES_FIRST): twiddle bases, the two split bases, the thread's window values
+  // tables first: twiddle bases, the two split bases, the thread's window values
   RegTwiddles<T, 12> twf;
   twf.load(tw, tid);
   // (W_16384^(2 tid), W_16384^(2 tid + 1)) in one 16-byte load: the first is W_8192^tid, base of the
@@ -2059,29 +1968,19 @@ spectrum_dif16k_kernel(const T *__restrict__ frames, const T *__restrict__ win, 
   load_order_fence();
 
   // z[m], z[m + 4096], m = tid + 256q: 8-byte non-temporal loads, unit stride across the lanes.
-  // Buffer form (PDSP_DIF_BUFFER): one descriptor for the frame, ONE per-lane offset register (8 tid) and
-  // the 2048 q (+ 32768) part as a scalar offset -- with flat addresses hipcc built a 64-bit vector address
-  // per load (v_add_co / s_nop / v_addc: the q offsets exceed the 13-bit immediate), ~100 of the kernel's
-  // ~1300 issue slots, on a kernel whose vector issue is its busiest resource.
-#ifndef PDSP_DIF_BUFFER
-#define PDSP_DIF_BUFFER 1
-#endif
+  // One buffer descriptor for the frame, ONE per-lane offset register (8 tid) and the 2048 q (+ 32768) part as a
+  // scalar offset -- with flat addresses hipcc built a 64-bit vector address per load (v_add_co / s_nop / v_addc:
+  // the q offsets exceed the 13-bit immediate), ~100 of the kernel's ~1300 issue slots, on a kernel whose vector
+  // issue is its busiest resource.
   const cx<T> *const z2 = reinterpret_cast<const cx<T> *>(frames + (size_t)row * (size_t)stride);
   cx<T> a[E], b[E];
-  if constexpr (PDSP_DIF_BUFFER && sizeof(T) == 4) {
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<cx<T> *>(z2), 0, 2 * M * (int)sizeof(T), 0x00020000);
-    const int vo = tid * 8;
-    static_for<E>([&](auto q) {
-      a[q] = __builtin_bit_cast(cx<T>, __builtin_amdgcn_raw_buffer_load_b64(rs, vo, 2048 * q, 2 /* nt */));
-      b[q] = __builtin_bit_cast(cx<T>, __builtin_amdgcn_raw_buffer_load_b64(rs, vo, 32768 + 2048 * q, 2));
-    });
-  } else {
-    static_for<E>([&](auto q) {
-      a[q] = ld_stream(z2 + TP * q + (unsigned)tid);
-      b[q] = ld_stream(z2 + H + TP * q + (unsigned)tid);
-    });
-  }
+  const __amdgpu_buffer_rsrc_t rs =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<cx<T> *>(z2), 0, 2 * M * (int)sizeof(T), 0x00020000);
+  const int vo = tid * 8;
+  static_for<E>([&](auto q) {
+    a[q] = __builtin_bit_cast(cx<T>, __builtin_amdgcn_raw_buffer_load_b64(rs, vo, 2048 * q, 2 /* nt */));
+    b[q] = __builtin_bit_cast(cx<T>, __builtin_amdgcn_raw_buffer_load_b64(rs, vo, 32768 + 2048 * q, 2));
+  });
   load_order_fence();
   // Every variant hands the sub-transforms a frame PRE-SCALED by g = s_mid / 2 (a power of two: exact), so that the
   // Hermitian split multiplies by nothing: the fused windows carry g in their coefficients (WinFused), the table
@@ -2188,13 +2087,8 @@ spectrum_dif16k_kernel(const T *__restrict__ frames, const T *__restrict__ win, 
       bestm.consider_descending(mbo, M - 1 - 2 * k, xbo);
     }
     if (store_amp) {
-      if constexpr (PDSP_DIF_BUFFER && sizeof(T) == 4) {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2s, V2{mae, mao}), ws, vo_lo, 2048 * q, 2 /* nt */);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2s, V2{mbo, mbe}), ws, vo_hi, 2048 * (7 - q), 2);
-      } else {
-        __builtin_nontemporal_store(V2{mae, mao}, reinterpret_cast<V2 *>(arow + (unsigned)(2 * k)));
-        __builtin_nontemporal_store(V2{mbo, mbe}, reinterpret_cast<V2 *>(arow + (unsigned)(M - 1 - 2 * k)));
-      }
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2s, V2{mae, mao}), ws, vo_lo, 2048 * q, 2 /* nt */);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U2s, V2{mbo, mbe}), ws, vo_hi, 2048 * (7 - q), 2);
     }
   });
   // the middle bin 4096 = 2*2048 pairs with itself: X[4096] = conj(Z[4096]) = conj(U[2048])
@@ -2202,7 +2096,7 @@ spectrum_dif16k_kernel(const T *__restrict__ frames, const T *__restrict__ win, 
     const cx<T> xm = conj(umid);
     const T mm = mag(xm) * T(2);  // the pre-scaled frame carries s_mid / 2; this bin is one value, not a sum of two
     if constexpr (PEAK) best.consider(mm, H, xm);
-    if (store_amp) st_rowtail(mm, arow + (unsigned)H);
+    if (store_amp) arow[(unsigned)H] = mm;
   }
 
   if constexpr (PEAK) {
@@ -2338,7 +2232,7 @@ tile_pass_kernel(const T *__restrict__ in_re, const T *__restrict__ in_im, T *__
   const int seg = t / TS, j4 = (t % TS) * 4;
 
   // COLS: the inter-pass twiddles W_N^(tmul (t0 + j4 + j) p), p = seg + SPI ic.  Tables first (the lesson of
-  // the single-pass kernels, PDSP_TABLES_FIRST): four two-level lookups per lane up here, their L2 latency
+  // the single-pass kernels, load_order_fence's header): four two-level lookups per lane up here, their L2 latency
   // under the tile's HBM loads, and one product per iteration below -- instead of four gathers per iteration
   // between the transforms and the stores.  With q = tmul << tshift, J = t0 + j4:
   //   w(ic)  = W^(q p J) = W^(q seg J) * (W^(q SPI J))^ic          first element of the lane's four

@@ -31,8 +31,8 @@ int fail(int code, const char *fmt, ...);
 // development switches (tools / tests): 0 routes N = 16384 spectra to spectrum_packed_kernel<13>,
 // and 32 <= N <= 256 transforms to the direct kernel instead of fft_staged_kernel
 extern int g_split16k;
-extern int g_fused_window;
-extern int g_twopass;       // pdsp_set_twopass: 2^15 <= N <= 2^18 f32 transforms in two passes (balanced factors)  // pdsp_set_fused_window: plan-owned cosine-sum windows evaluated in the kernel
+extern int g_fused_window;  // pdsp_set_fused_window: plan-owned cosine-sum windows evaluated in the kernel
+extern int g_twopass;       // pdsp_set_twopass: 2^15 <= N <= 2^18 f32 transforms in two passes (balanced factors)
 extern int g_split8k_f32;  // f32 N = 8192 rows on fft_split2_kernel too (A/B: pdsp_set_split16k bit 1)
 extern int g_staged_small;
 extern int g_real_packed;  // pdsp_set_real_packed: Radix2Fft.forward rows of 512 <= N <= 16384 on fft_real_kernel
@@ -45,9 +45,8 @@ extern int g_real_packed;  // pdsp_set_real_packed: Radix2Fft.forward rows of 51
       return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at %s", (int)e_, hipGetErrorString(e_), #expr); \
   } while (0)
 
-// Stream-ordered scratch that is handed back on every exit path.
-// Stream-ordered scratch planes of the multi-pass paths, from a pool of the engine's own per device whose release
-// threshold is unlimited: the device's default pool hands its memory back at every synchronisation, so that a
+// Stream-ordered scratch planes of the multi-pass paths, handed back on every exit path, from a pool of the
+// engine's own per device whose release threshold is unlimited: the device's default pool hands its memory back at every synchronisation, so that a
 // caller who synchronises between transforms (every host-f64 call does) paid a fresh 1-2 GiB allocation --
 // a trip through the kernel driver, observed to stall for 0.5-1 s on a busy host -- on each call.  Here the planes
 // of the largest transform seen stay with the engine until pdsp_plan_cache_clear() trims the pools.
@@ -220,12 +219,16 @@ inline int grid_for(long long total) {
   return (int)b;
 }
 
+// A launch of `blocks` workgroups for `batch` rows must fit grid.x (2^31 - 1)
+inline int check_grid(long long blocks, long long batch) {
+  if (blocks > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+  return PDSP_OK;
+}
+
 inline int check_plan_batch(const pdsp_plan *plan, long long batch) {
   if (!plan) return fail(PDSP_ERR_BAD_ARG, "plan is null");
   if (batch < 0) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 0, got %lld", batch);
-  // grid.x limit; far beyond any HBM-resident batch
-  if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
-  return PDSP_OK;
+  return check_grid(batch, batch);  // one workgroup per row at most; far beyond any HBM-resident batch
 }
 
 // ---- kernel dispatchers: defined in pdsp_dispatch.inc, instantiated for float / double in the kernel units -------
