@@ -355,6 +355,60 @@ PDSP_API int pdsp_spectrum_rows_host_f32in(const float *const *rows, long long b
                                            double *freq_out, double *amp_out, double *phase_out,
                                            pdsp_peak *peak_out, long long *bins_out);
 
+/* ---- FIR filtering (fused overlap-save), f32 / f64 ------------------------ */
+/* Linear convolution y = x * h of many real rows with one real FIR filter of ntaps taps: the
+ * "FIR helpers, convolution ... frequency response analysis via FFT utilities" of the reference's
+ * roadmap (ROADMAP.md, "Filters and utilities": the pragma-dsp/filters module); the reference has
+ * no such function yet.  Its FFT-domain form there is forward -> multiply -> inverse
+ * (test/fluent/chain.test.ts:287-317); here that chain runs as ONE launch per call: each block of
+ * N = pdsp_plan_size() samples is loaded once, transformed (packed-real, N/2 points), multiplied by
+ * H, transformed back and its last N - ntaps + 1 samples stored -- overlap-save with
+ * hop = N - ntaps + 1, nothing in between in HBM.  Filters longer than N/2 taps (partitioned
+ * convolution) are not supported: PDSP_ERR_UNSUPPORTED_SIZE.  So are IIR filters, per-row filters,
+ * complex signals and state carried across calls.
+ * Validation happens before any device work: ntaps < 1, a negative batch / length / offset / stride,
+ * outputs beyond the full convolution, a batch whose extent overflows 64 bits or whose blocks
+ * overflow the grid give PDSP_ERR_BAD_ARG; a plan outside 64 <= N <= 16384 or ntaps > N/2 gives
+ * PDSP_ERR_UNSUPPORTED_SIZE.  f32: ~1e-7 of max|x| * sum|h|; f64: ~1e-16. */
+
+/* H[k] = sum_j taps[j] e^{-j 2 pi j k / N}, k = 0 ... N/2 (N/2 + 1 device values per plane): the
+ * filter's frequency response sampled at the plan's N -- what pdsp_fir_filter_* reads, and useful on
+ * its own.  Computed once per filter, summed in f64 with exact twiddle arguments.  ntaps <= N/2. */
+PDSP_API int pdsp_fir_spectrum_f32(const pdsp_plan *plan, const float *taps, long long ntaps,
+                                   float *h_re, float *h_im, pdsp_stream stream);
+PDSP_API int pdsp_fir_spectrum_f64(const pdsp_plan *plan, const double *taps, long long ntaps,
+                                   double *h_re, double *h_im, pdsp_stream stream);
+/* y[r][i] = sum_j taps[j] * x[r][y_off + i - j], x zero outside [0, len), for 0 <= i < y_len and
+ * rows r < batch at strides x_stride / y_stride (device pointers, any alignment); h_re / h_im from
+ * pdsp_fir_spectrum_* of the same plan and ntaps.  y_off + y_len <= len + ntaps - 1; y_stride >= y_len
+ * when batch > 1; y must not overlap x.  8-byte aligned rows with even strides and an even y_off take
+ * the 8-byte load / store path (an even ntaps runs with one zero tap more, so that hop is even). */
+PDSP_API int pdsp_fir_filter_f32(const pdsp_plan *plan, long long batch, const float *x, long long len,
+                                 long long x_stride, const float *h_re, const float *h_im, long long ntaps,
+                                 long long y_off, long long y_len, float *y, long long y_stride,
+                                 pdsp_stream stream);
+PDSP_API int pdsp_fir_filter_f64(const pdsp_plan *plan, long long batch, const double *x, long long len,
+                                 long long x_stride, const double *h_re, const double *h_im, long long ntaps,
+                                 long long y_off, long long y_len, double *y, long long y_stride,
+                                 pdsp_stream stream);
+
+typedef enum pdsp_fir_mode {    /* output range, counted in the full convolution; m = min(len, ntaps) */
+  PDSP_FIR_FULL = 0,            /* numpy.convolve "full":  offset 0,         length len + ntaps - 1 */
+  PDSP_FIR_SAME = 1,            /* numpy.convolve "same":  offset (m-1)/2,   length max(len, ntaps) */
+  PDSP_FIR_VALID = 2,           /* numpy.convolve "valid": offset m - 1,     length |len - ntaps| + 1 */
+  PDSP_FIR_FILTER = 3           /* scipy.signal.lfilter(taps, 1, x): offset 0, length len */
+} pdsp_fir_mode;
+/* (y_off, y_len) of a mode for a signal of len >= 1 samples and ntaps >= 1 taps (no device work). */
+PDSP_API int pdsp_fir_output_range(long long len, long long ntaps, int mode, long long *y_off,
+                                   long long *y_len);
+/* The block size N the host form uses for ntaps taps (1 ... 8192; 0 outside): the smallest power of
+ * two >= 8 * ntaps, at least 4096 and at most 16384 ("FIR filtering"). */
+PDSP_API long long pdsp_fir_block_size(long long ntaps);
+/* Host f64 drop-in form (synchronous, f64 arithmetic): `batch` contiguous rows of len >= 1 samples
+ * filtered by ntaps <= 8192 taps; y receives batch rows of the mode's length (pdsp_fir_output_range). */
+PDSP_API int pdsp_fir_filter_host_f64(const double *x, long long batch, long long len, const double *taps,
+                                      long long ntaps, int mode, double *y);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ ERR_DEVICE = 10
 
 WINDOW_TYPES = {"rect": 0, "hann": 1, "hamming": 2, "blackman": 3}
 SIDES = {"one": 0, "two": 1}
+FIR_MODES = {"full": 0, "same": 1, "valid": 2, "filter": 3}
 COMPLEX_OPS = {"add": 0, "sub": 1, "mul": 2, "div": 3, "conj": 4, "scale": 5, "mulScalar": 6}
 
 
@@ -119,6 +120,13 @@ def _load() -> C.CDLL:
         "pdsp_spectrum_batch_host_f64": ([dp, ll, ll, dbl, ll, i32, i32, dp, dp, dp, C.POINTER(Peak), C.POINTER(ll)], i32),
         "pdsp_spectrum_rows_host_f64": ([C.POINTER(dp), ll, ll, dbl, ll, i32, i32, dp, dp, dp, C.POINTER(Peak), C.POINTER(ll)], i32),
         "pdsp_spectrum_rows_host_f32in": ([C.POINTER(C.POINTER(C.c_float)), ll, ll, dbl, ll, i32, i32, dp, dp, dp, C.POINTER(Peak), C.POINTER(ll)], i32),
+        "pdsp_fir_spectrum_f32": ([vp, vp, ll, vp, vp, vp], i32),
+        "pdsp_fir_spectrum_f64": ([vp, vp, ll, vp, vp, vp], i32),
+        "pdsp_fir_filter_f32": ([vp, ll, vp, ll, ll, vp, vp, ll, ll, ll, vp, ll, vp], i32),
+        "pdsp_fir_filter_f64": ([vp, ll, vp, ll, ll, vp, vp, ll, ll, ll, vp, ll, vp], i32),
+        "pdsp_fir_output_range": ([ll, ll, i32, C.POINTER(ll), C.POINTER(ll)], i32),
+        "pdsp_fir_block_size": ([ll], ll),
+        "pdsp_fir_filter_host_f64": ([dp, ll, ll, dp, ll, i32, dp], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -1,12 +1,13 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from four translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from five translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
 //   pdsp_kernels_f32_fft.hip      run_complex<float>, run_interleaved<float>, element-wise f32 kernels
 //   pdsp_kernels_f32_spectrum.hip spectrum_impl<float> (fused spectrum kernels, findPeak kernels)
 //   pdsp_kernels_f64.hip          every dispatcher for double
+//   pdsp_kernels_fir.hip          FIR filtering (fused overlap-save) and the filter spectrum, f32 and f64
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -250,5 +251,14 @@ int polar_dev(long long count, const T *re, const T *im, T *out, hipStream_t s);
 // pdsp_complex_op_f32 after validation: op is a pdsp_complex_op
 int complex_op_f32(int op, long long count, const float *are, const float *aim, const float *bre, const float *bim,
                    long long b_len, float sre, float sim, float *ore, float *oim, hipStream_t s);
+
+// pdsp_fir_filter_* / pdsp_fir_spectrum_* after validation (pdsp_kernels_fir.hip): p = the taps the kernel runs with
+// (ntaps, or ntaps + 1 zero tap for an even hop), nblk = blocks of hop = N - p + 1 outputs per row, len >= 1
+template <typename T>
+int fir_filter_dev(const pdsp_plan *plan, long long batch, const T *x, long long len, long long x_stride,
+                   const T *h_re, const T *h_im, int p, long long y_off, long long y_len, T *y, long long y_stride,
+                   long long nblk, hipStream_t s);
+template <typename T>
+int fir_spectrum_dev(const pdsp_plan *plan, const T *taps, int ntaps, T *h_re, T *h_im, hipStream_t s);
 
 }  // namespace pdsp_host

@@ -543,6 +543,27 @@ static napi_value DeviceCount(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* firFilter(signal, taps, mode, out) -> out holds the mode's outputs (pdsp_fir_output_range)
+ * [pragma-dsp/filters of ROADMAP.md, "Filters and utilities"; include/pdsp_hip.h, "FIR filtering"] */
+static napi_value FirFilter(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return NULL;
+  double *x, *h, *y;
+  size_t nx, nh, ny;
+  int64_t mode;
+  if (!f64_array(env, argv[0], &x, &nx) || !f64_array(env, argv[1], &h, &nh) || !get_i64(env, argv[2], &mode) ||
+      !f64_array(env, argv[3], &y, &ny))
+    return NULL;
+  long long y_off = 0, y_len = 0;
+  if (pdsp_fir_output_range((long long)nx, (long long)nh, (int)mode, &y_off, &y_len) != PDSP_OK) return throw_pdsp(env);
+  if ((long long)ny < y_len) {
+    napi_throw_error(env, NULL, "pdsp_napi: firFilter output too small");
+    return NULL;
+  }
+  if (pdsp_fir_filter_host_f64(x, 1, (long long)nx, h, (long long)nh, (int)mode, y) != PDSP_OK) return throw_pdsp(env);
+  return NULL;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   const struct {
     const char *name;
@@ -554,6 +575,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"spectrum", Spectrum},     {"binFrequencies", BinFrequencies}, {"fftShift", FftShift},
       {"spectrumBatch", SpectrumBatch}, {"spectrumRows", SpectrumRows},
       {"nextPow2", NextPow2},     {"deviceCount", DeviceCount},
+      {"firFilter", FirFilter},
   };
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
     napi_value f;

@@ -1,10 +1,12 @@
 // Export map of the host module: the three reference surfaces that sit on the hot path.
 import * as coreNs from './core';
 import * as fourierNs from './fourier';
+import * as filtersNs from './filters';
 
 export { spectrum, spectrumBatch, spectrumStream, SpectrumOptions, SpectrumPeak, SpectrumResult } from './spectrum';
 export { ComplexArray } from './core';
 export { WindowType } from './fourier';
+export { FirMode, FirFilterOptions } from './filters';
 
 export const core: {
   createComplexArray: typeof coreNs.createComplexArray;
@@ -21,4 +23,7 @@ export const fourier: {
   fftShift: typeof fourierNs.fftShift;
   fftShiftComplex: typeof fourierNs.fftShiftComplex;
   binFrequencies: typeof fourierNs.binFrequencies;
+};
+export const filters: {
+  firFilter: typeof filtersNs.firFilter;
 };

