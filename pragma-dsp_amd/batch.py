@@ -49,8 +49,8 @@ class PlanWindow:
 
 class BatchedFft:
     """One plan, many rows.  Tensors are contiguous, shape [..., N], on the plan's GPU, of the
-    plan's dtype: torch.float32 (default; every size up to 16384) or torch.float64 (complex
-    transforms up to N = 8192, spectrum up to N = 16384)."""
+    plan's dtype: torch.float32 (default; sizes up to 2^28) or torch.float64 (up to 2^26; single-pass
+    transforms up to N = 8192, spectrum up to N = 16384, four-step beyond)."""
 
     def __init__(self, size, device=None, dtype=torch.float32):
         if dtype not in (torch.float32, torch.float64):
@@ -213,10 +213,18 @@ class BatchedFft:
         truncated: spectrum.ts:36-43) -> amplitude [..., bins] (+ phase, + peak bin)."""
         if frames.dtype != self.dtype or not frames.is_cuda or not frames.is_contiguous():
             raise PdspError(_capi.ERR_BAD_ARG, f"frames must be a contiguous {self.dtype} CUDA tensor")
+        if frames.get_device() != self.device.index:
+            raise PdspError(_capi.ERR_BAD_ARG, f"frames are on {frames.device}, plan is on {self.device}")
         length = frames.shape[-1]
         batch = frames.numel() // length if length else 0
         two = sides != "one"
         bins = self.size if two else self.size // 2 + 1
+        shape = tuple(frames.shape[:-1])
+        # the amplitude rows are written through a raw pointer: exactly [..., bins], contiguous, on the plan's device
+        if out is not None and (out.get_device() != self.device.index or out.dtype != self.dtype
+                                or not out.is_contiguous() or out.shape != shape + (bins,)):
+            raise PdspError(_capi.ERR_BAD_ARG, f"out must be a contiguous {self.dtype} tensor of shape "
+                                               f"{shape + (bins,)} on {self.device}")
         if isinstance(window, str):
             if self.size != 1 and window not in _capi.WINDOW_TYPES:
                 raise PdspError(_capi.ERR_WINDOW_TYPE, f"Unsupported window type: {window}")
@@ -228,7 +236,6 @@ class BatchedFft:
                     raise PdspError(_capi.ERR_WINDOW_LENGTH, "Window length must match input length.")
                 if not isinstance(win, PlanWindow):
                     self._check(win, "window")
-        shape = tuple(frames.shape[:-1])
         amp = out if out is not None else torch.empty(shape + (bins,), dtype=self.dtype, device=self.device)
         ph = torch.empty(shape + (bins,), dtype=self.dtype, device=self.device) if want_phase else None
         pk = torch.empty(shape, dtype=torch.int32, device=self.device) if want_peak else None
@@ -245,6 +252,8 @@ class BatchedFft:
         (amplitude [frames, bins], phase or None, peak bin or None)."""
         if signal.dim() != 1 or signal.dtype != self.dtype or not signal.is_cuda or not signal.is_contiguous():
             raise PdspError(_capi.ERR_BAD_ARG, f"signal must be a contiguous 1-D {self.dtype} CUDA tensor")
+        if signal.get_device() != self.device.index:
+            raise PdspError(_capi.ERR_BAD_ARG, f"signal is on {signal.device}, plan is on {self.device}")
         if hop < 1:
             raise PdspError(_capi.ERR_BAD_ARG, f"hop must be >= 1, got {hop}")
         n = self.size
@@ -273,6 +282,8 @@ class BatchedFft:
             raise PdspError(_capi.ERR_BAD_ARG, "spectrum_peaks is f32 only (16-byte f32 records)")
         if frames.dtype != torch.float32 or not frames.is_cuda or not frames.is_contiguous():
             raise PdspError(_capi.ERR_BAD_ARG, "frames must be a contiguous float32 CUDA tensor")
+        if frames.get_device() != self.device.index:
+            raise PdspError(_capi.ERR_BAD_ARG, f"frames are on {frames.device}, plan is on {self.device}")
         if sample_rate <= 0:
             raise PdspError(_capi.ERR_SAMPLE_RATE, f"Sample rate must be positive, got {js_num(sample_rate)}")
         length = frames.shape[-1]
@@ -297,42 +308,91 @@ class BatchedFft:
 
 
 # -- stand-alone element-wise device helpers ----------------------------------
+# The library reads and writes these operands through raw pointers with no shape of their own, so every operand is
+# checked here, before any library call: a CUDA tensor, contiguous, on the device and of the dtype of the first
+# operand, with the element count the call reads or writes.
+
+_SFX = {torch.float32: "f32", torch.float64: "f64"}
+
+
+def _check_operand(t, name, like=None, numel=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be a CUDA tensor")
+    if like is not None and t.device != like.device:
+        raise PdspError(_capi.ERR_BAD_ARG, f"{name} is on {t.device}, the first operand on {like.device}")
+    if like is not None and t.dtype != like.dtype:
+        raise PdspError(_capi.ERR_BAD_ARG, f"{name} is {t.dtype}, the first operand {like.dtype}")
+    if not t.is_contiguous():
+        raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be contiguous")
+    if numel is not None and t.numel() != numel:
+        raise PdspError(_capi.ERR_INPUT_LENGTH, f"{name} has {t.numel()} elements, {numel} expected")
+
+
+def _sfx(t, what):
+    sfx = _SFX.get(t.dtype)
+    if sfx is None:
+        raise PdspError(_capi.ERR_BAD_ARG, f"{what}: unsupported dtype {t.dtype} (float32 or float64)")
+    return sfx
+
 
 def apply_window(frames: torch.Tensor, window: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    if frames.shape[-1] != window.shape[-1]:
+    _check_operand(frames, "frames")
+    sfx = _sfx(frames, "apply_window")
+    _check_operand(window, "window", frames)
+    n = frames.shape[-1] if frames.dim() else 1
+    if window.numel() != n or window.shape[-1:] != (n,):
         raise PdspError(_capi.ERR_WINDOW_LENGTH, "Window length must match input length.")
+    if out is not None:
+        _check_operand(out, "out", frames, frames.numel())
     out = torch.empty_like(frames) if out is None else out
-    n = frames.shape[-1]
-    check(lib.pdsp_apply_window_f32(frames.numel() // n if n else 0, n, _ptr(frames), _ptr(window), _ptr(out),
-                                    _stream_ptr(frames.device)))
+    check(getattr(lib, "pdsp_apply_window_" + sfx)(frames.numel() // n if n else 0, n, _ptr(frames), _ptr(window),
+                                                   _ptr(out), _stream_ptr(frames.device)))
+    return out
+
+
+def _polar(name, re, im, out):
+    _check_operand(re, "re")
+    sfx = _sfx(re, name)
+    _check_operand(im, "im", re, re.numel())
+    if out is not None:
+        _check_operand(out, "out", re, re.numel())
+    out = torch.empty_like(re) if out is None else out
+    check(getattr(lib, f"pdsp_{name}_{sfx}")(re.numel(), _ptr(re), _ptr(im), _ptr(out), _stream_ptr(re.device)))
     return out
 
 
 def magnitude(re: torch.Tensor, im: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    out = torch.empty_like(re) if out is None else out
-    check(lib.pdsp_magnitude_f32(re.numel(), _ptr(re), _ptr(im), _ptr(out), _stream_ptr(re.device)))
-    return out
+    """|re + i im| element-wise (f64: hypot, no overflow or underflow of the squares)."""
+    return _polar("magnitude", re, im, out)
 
 
 def phase(re: torch.Tensor, im: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    out = torch.empty_like(re) if out is None else out
-    check(lib.pdsp_phase_f32(re.numel(), _ptr(re), _ptr(im), _ptr(out), _stream_ptr(re.device)))
-    return out
+    return _polar("phase", re, im, out)
 
 
 # -- element-wise complex vector arithmetic (src/math/complex.ts) on device rows ------
 
 def _complex_op(name, a, b=None, s_re=0.0, s_im=0.0, out=None):
     are, aim = a
-    ore, oim = (torch.empty_like(are), torch.empty_like(aim)) if out is None else out
+    _check_operand(are, "a.real")
+    if are.dtype != torch.float32:
+        raise PdspError(_capi.ERR_BAD_ARG, f"complex_{name} is float32 only, got {are.dtype}")
+    count = are.numel()
+    _check_operand(aim, "a.imag", are, count)
     bre = bim = None
     b_len = 0
     if b is not None:
         bre, bim = b
+        _check_operand(bre, "b.real", are)
         b_len = bre.numel()
-        if are.numel() % max(b_len, 1) != 0:
-            raise PdspError(_capi.ERR_BAD_ARG, f"second operand length {b_len} must divide {are.numel()}")
-    check(lib.pdsp_complex_op_f32(_capi.COMPLEX_OPS[name], are.numel(), _ptr(are), _ptr(aim), _ptr(bre), _ptr(bim),
+        _check_operand(bim, "b.imag", are, b_len)
+        if (b_len == 0 and count != 0) or (b_len and count % b_len != 0):
+            raise PdspError(_capi.ERR_BAD_ARG, f"second operand length {b_len} must divide {count}")
+    if out is not None:
+        _check_operand(out[0], "out.real", are, count)
+        _check_operand(out[1], "out.imag", are, count)
+    ore, oim = (torch.empty_like(are), torch.empty_like(aim)) if out is None else out
+    check(lib.pdsp_complex_op_f32(_capi.COMPLEX_OPS[name], count, _ptr(are), _ptr(aim), _ptr(bre), _ptr(bim),
                                   b_len, float(s_re), float(s_im), _ptr(ore), _ptr(oim), _stream_ptr(are.device)))
     return ore, oim
 

@@ -116,6 +116,13 @@ def test_f64_device_family(oracle_mod, log2n):
     win = oracle_mod.create_window("hann", n) if n > 1 else None
     wamp, wph, wpk = oracle_mod.Plan(n).spectrum_batch(re, window=win, want_phase=True, want_peak=True)
     assert rel_err(amp.cpu().numpy(), wamp) <= 1e-14
+    top = wamp.max(axis=-1, keepdims=True)
+    mask = wamp > 1e-6 * top
+    d = np.abs((ph.cpu().numpy() - wph + np.pi) % (2 * np.pi) - np.pi)
+    assert d[mask].max(initial=0) <= 1e-9
+    p = pk.cpu().numpy()
+    for b in range(len(p)):  # the oracle's bin, or one whose amplitude ties with it to f64 rounding
+        assert p[b] == wpk[b] or abs(wamp[b, p[b]] - wamp[b, wpk[b]]) <= 1e-13 * top[b, 0]
 
 
 def test_f64_limits(pdsp):
