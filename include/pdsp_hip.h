@@ -381,7 +381,8 @@ PDSP_API int pdsp_fir_spectrum_f64(const pdsp_plan *plan, const double *taps, lo
 /* y[r][i] = sum_j taps[j] * x[r][y_off + i - j], x zero outside [0, len), for 0 <= i < y_len and
  * rows r < batch at strides x_stride / y_stride (device pointers, any alignment); h_re / h_im from
  * pdsp_fir_spectrum_* of the same plan and ntaps.  y_off + y_len <= len + ntaps - 1; y_stride >= y_len
- * when batch > 1; y must not overlap x.  8-byte aligned rows with even strides and an even y_off take
+ * when batch > 1; y must not overlap x: a y whose byte extent ((batch - 1) * y_stride + y_len elements)
+ * meets that of x gives PDSP_ERR_BAD_ARG before any launch.  8-byte aligned rows with even strides and an even y_off take
  * the 8-byte load / store path (an even ntaps runs with one zero tap more, so that hop is even). */
 PDSP_API int pdsp_fir_filter_f32(const pdsp_plan *plan, long long batch, const float *x, long long len,
                                  long long x_stride, const float *h_re, const float *h_im, long long ntaps,

@@ -1496,6 +1496,13 @@ int fir_filter_t(const pdsp_plan *plan, long long batch, const T *x, long long l
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
   if (batch == 0 || y_len == 0) return PDSP_OK;
   if (!y || (len > 0 && (!x || !h_re || !h_im))) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  // blocks of a row read input that other blocks overwrite when y shares bytes with x: the result would depend on
+  // the order in which workgroups run.  Byte ranges of the whole strided extent, as planes_overlap()
+  if (len > 0) {
+    const char *xb = (const char *)x, *yb = (const char *)y;
+    const size_t xn = (size_t)((batch - 1) * x_stride + len) * sizeof(T), yn = (size_t)((batch - 1) * y_stride + y_len) * sizeof(T);
+    if (xb < yb + yn && yb < xb + xn) return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
+  }
   // an even filter runs with one zero tap more (same H): P odd makes hop = N - P + 1 even, the aligned fast path
   const int p = (int)(ntaps % 2 == 1 ? ntaps : ntaps + 1);
   const long long hop = plan->n - (p - 1);

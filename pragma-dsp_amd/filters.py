@@ -82,11 +82,20 @@ class FirFilter:
         self.h_im = torch.empty(bins, dtype=dtype, device=self.device)
         with torch.cuda.device(self.device):
             fn = getattr(lib, f"pdsp_fir_spectrum_{self._sfx}")
+            stream = torch.cuda.current_stream(self.device)
             check(fn(self.plan._h, C.c_void_p(self.taps.data_ptr()), self.ntaps, C.c_void_p(self.h_re.data_ptr()),
-                     C.c_void_p(self.h_im.data_ptr()), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                     C.c_void_p(self.h_im.data_ptr()), C.c_void_p(stream.cuda_stream)))
+            # H is written on the stream current at construction; apply() may run on another one
+            self._ready = torch.cuda.Event()
+            self._ready.record(stream)
+
+    def _wait_ready(self):
+        torch.cuda.current_stream(self.device).wait_event(self._ready)
 
     def frequency_response(self):
-        """H[k] = sum_j taps[j] e^{-2 pi i j k / N}, k = 0 ... N/2, as two device tensors (re, im)."""
+        """H[k] = sum_j taps[j] e^{-2 pi i j k / N}, k = 0 ... N/2, as two device tensors (re, im), ordered on the
+        current stream."""
+        self._wait_ready()
         return self.h_re, self.h_im
 
     def apply(self, x: torch.Tensor, mode: str = "full", out: torch.Tensor | None = None) -> torch.Tensor:
@@ -103,6 +112,7 @@ class FirFilter:
             raise PdspError(_capi.ERR_BAD_ARG, f"out must be a {self.dtype} tensor of shape {(*x.shape[:-1], y_len)}")
         _, y_stride = _rows(out, "out")
         with torch.cuda.device(self.device):
+            self._wait_ready()
             fn = getattr(lib, f"pdsp_fir_filter_{self._sfx}")
             check(fn(self.plan._h, rows, C.c_void_p(x.data_ptr()), length, x_stride, C.c_void_p(self.h_re.data_ptr()),
                      C.c_void_p(self.h_im.data_ptr()), self.ntaps, y_off, y_len, C.c_void_p(out.data_ptr()), y_stride,
