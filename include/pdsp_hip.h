@@ -410,6 +410,47 @@ PDSP_API long long pdsp_fir_block_size(long long ntaps);
 PDSP_API int pdsp_fir_filter_host_f64(const double *x, long long batch, long long len, const double *taps,
                                       long long ntaps, int mode, double *y);
 
+/* ---- short-time transform (complex bins) and its overlap-add inverse, f32 / f64 -------------- */
+/* The reference's roadmap "A) STFT" (ROADMAP.md: pragma-dsp/xform/stft, stft(signal, opts) with complex output),
+ * and the way back to the time domain.  N = pdsp_plan_size(), 64 <= N <= 16384 in both precisions (any other
+ * power of two: PDSP_ERR_UNSUPPORTED_SIZE); window = NULL (rect), a plan table (pdsp_plan_window_*) or any N device
+ * values.  Every argument is checked before any device work: a null plan or buffer, frames < 1, hop < 1, extents
+ * that overflow 64 bits or a grid of 2^31 frames give PDSP_ERR_BAD_ARG, and so does an output whose byte extent
+ * meets an input's (or the other output plane's). */
+
+/* X_b[k] = sum_{n < N} w[n] x_b[n] e^{-2 pi i k n / N}, k = 0 ... N/2, unscaled (numpy.fft.rfft(w * frame)):
+ * the framing of pdsp_spectrum_f32 -- `batch` frames at frame_stride, the first min(frame_len, N) samples used, zero
+ * beyond; frame_stride = hop < frame_len reads overlapping frames of one signal in place.  re_out / im_out:
+ * [batch][N/2 + 1] each.  One launch, the packed-real forward + Hermitian split; f32 ~1e-7 * sqrt(log2 N) of
+ * max|X|, f64 ~1e-16. */
+PDSP_API int pdsp_stft_complex_f32(const pdsp_plan *plan, long long batch, const float *frames,
+                                   long long frame_len, long long frame_stride, const float *window,
+                                   float *re_out, float *im_out, pdsp_stream stream);
+PDSP_API int pdsp_stft_complex_f64(const pdsp_plan *plan, long long batch, const double *frames,
+                                   long long frame_len, long long frame_stride, const double *window,
+                                   double *re_out, double *im_out, pdsp_stream stream);
+/* Weighted overlap-add inverse of `frames` >= 1 rows of N/2 + 1 bins (re_in / im_in [frames][N/2 + 1]):
+ * y_b = irfft(X_b, N) (1/N; the imaginary parts of bins 0 and N/2 ignored), out has T = (frames - 1) hop + N samples,
+ *   out[t] = sum_b w[t - b hop] y_b[t - b hop] / sum_b w[t - b hop]^2   over the frames covering t, ascending b,
+ * and 0 where the denominator is <= 1e-11 (ends of the symmetric Hann, the gaps of hop > N).  This is
+ * torch.istft(center=False, onesided=True) wherever its NOLA check passes.  hop >= N: one launch, no scratch;
+ * hop < N: a frame pass into stream-ordered scratch and a gather pass per chunk of S frames, K = ceil(N/hop) - 1
+ * frames recomputed per chunk, scratch min(S + K, frames) rows of N values, S = max(K + 1, 2^28 bytes / (N sizeof T)
+ * - K): at most max(256 MiB, (2K + 1) N sizeof T) whatever `frames` is (256 MiB for hop >= N/64 up to N = 16384).  No atomics: bit-identical results from call to call
+ * and for every chunk size.  f32 ~1e-7 * log2 N of max|y|, f64 ~1e-16 * log2 N (relative to the frames' scale). */
+PDSP_API int pdsp_istft_f32(const pdsp_plan *plan, long long frames, const float *re_in, const float *im_in,
+                            long long hop, const float *window, float *out, pdsp_stream stream);
+PDSP_API int pdsp_istft_f64(const pdsp_plan *plan, long long frames, const double *re_in, const double *im_in,
+                            long long hop, const double *window, double *out, pdsp_stream stream);
+/* Host f64 forms (synchronous, f64 arithmetic, window_type a pdsp_window): signal of len >= fft_size samples
+ * (PDSP_ERR_INPUT_LENGTH otherwise), F = 1 + (len - fft_size) / hop frames (the tail shorter than a hop is
+ * ignored); re_out / im_out [F][fft_size/2 + 1]. */
+PDSP_API int pdsp_stft_host_f64(const double *signal, long long len, long long fft_size, long long hop,
+                                int window_type, double *re_out, double *im_out);
+/* out: (frames - 1) hop + fft_size samples, as pdsp_istft_f64. */
+PDSP_API int pdsp_istft_host_f64(const double *re, const double *im, long long frames, long long fft_size,
+                                 long long hop, int window_type, double *out);
+
 #ifdef __cplusplus
 }
 #endif

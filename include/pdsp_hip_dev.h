@@ -49,6 +49,11 @@ PDSP_API int pdsp_set_twopass(int enabled);
  * (DESIGN 4.1c). */
 PDSP_API int pdsp_set_real_packed(int enabled);
 
+/* Frames per chunk of the two-pass inverse short-time transform (pdsp_istft_*, hop < N): 0 (default) = the bound
+ * stated in pdsp_hip.h, n >= 1 = n frames (capped so that a chunk's outputs fit one grid).  Results are bit-identical
+ * for every value; tests use small ones to run many chunks on small inputs.  Returns the previous value. */
+PDSP_API int pdsp_set_istft_chunk_frames(int frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,13 @@ def _load() -> C.CDLL:
         "pdsp_fir_output_range": ([ll, ll, i32, C.POINTER(ll), C.POINTER(ll)], i32),
         "pdsp_fir_block_size": ([ll], ll),
         "pdsp_fir_filter_host_f64": ([dp, ll, ll, dp, ll, i32, dp], i32),
+        "pdsp_stft_complex_f32": ([vp, ll, vp, ll, ll, vp, vp, vp, vp], i32),
+        "pdsp_stft_complex_f64": ([vp, ll, vp, ll, ll, vp, vp, vp, vp], i32),
+        "pdsp_istft_f32": ([vp, ll, vp, vp, ll, vp, vp, vp], i32),
+        "pdsp_istft_f64": ([vp, ll, vp, vp, ll, vp, vp, vp], i32),
+        "pdsp_stft_host_f64": ([dp, ll, ll, ll, i32, dp, dp], i32),
+        "pdsp_istft_host_f64": ([dp, dp, ll, ll, ll, i32, dp], i32),
+        "pdsp_set_istft_chunk_frames": ([i32], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -272,6 +272,75 @@ class BatchedFft:
                                                          _ptr(amp), _ptr(ph), _ptr(pk), _stream_ptr(self.device)))
         return amp, ph, pk
 
+    def _table_window(self, window, name="window"):
+        """A window argument of the short-time pair: a type name (the plan's table; "rect" = none), a PlanWindow of
+        this plan, or a contiguous device tensor of N values in the plan's dtype."""
+        if isinstance(window, str):
+            if window not in _capi.WINDOW_TYPES:
+                raise PdspError(_capi.ERR_WINDOW_TYPE, f"Unsupported window type: {window}")
+            return None if window == "rect" else self.window(window)
+        if isinstance(window, PlanWindow):
+            if window._plan is not self:
+                raise PdspError(_capi.ERR_BAD_ARG, f"{name} belongs to another plan")
+            return window
+        if not isinstance(window, torch.Tensor):
+            raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be a window type name or a device tensor")
+        if window.dim() != 1 or window.shape[0] != self.size:
+            raise PdspError(_capi.ERR_WINDOW_LENGTH, "Window length must match input length.")
+        self._check(window, name)
+        return window
+
+    def stft_complex(self, signal: torch.Tensor, hop: int, window="hann"):
+        """Complex short-time transform of one contiguous 1-D signal: frame b = signal[b*hop : b*hop + N], the tail
+        shorter than a hop ignored (as stft()).  Returns (re, im), each [frames, N/2 + 1]: the one-sided DFT of
+        w * frame, unscaled.  One launch; the frames are read in place at row stride `hop`.  64 <= N <= 16384."""
+        if not isinstance(signal, torch.Tensor) or signal.dim() != 1 or signal.dtype != self.dtype or not signal.is_cuda \
+                or not signal.is_contiguous():
+            raise PdspError(_capi.ERR_BAD_ARG, f"signal must be a contiguous 1-D {self.dtype} CUDA tensor")
+        if signal.get_device() != self.device.index:
+            raise PdspError(_capi.ERR_BAD_ARG, f"signal is on {signal.device}, plan is on {self.device}")
+        if int(hop) < 1:
+            raise PdspError(_capi.ERR_BAD_ARG, f"hop must be >= 1, got {hop}")
+        n = self.size
+        if signal.numel() < n:
+            raise PdspError(_capi.ERR_INPUT_LENGTH, f"signal length {signal.numel()} is shorter than one frame ({n})")
+        win = self._table_window(window)
+        frames = 1 + (signal.numel() - n) // int(hop)
+        re = torch.empty((frames, n // 2 + 1), dtype=self.dtype, device=self.device)
+        im = torch.empty_like(re)
+        check(getattr(lib, "pdsp_stft_complex_" + self._sfx)(self._h, frames, _ptr(signal), n, int(hop), _ptr(win),
+                                                             _ptr(re), _ptr(im), _stream_ptr(self.device)))
+        return re, im
+
+    def istft(self, re: torch.Tensor, im: torch.Tensor, hop: int, window="hann", out: torch.Tensor | None = None):
+        """Weighted overlap-add inverse of complex bins re / im [frames, N/2 + 1] (include/pdsp_hip.h,
+        pdsp_istft_*): [(frames - 1) * hop + N] samples, sum_b w y_b / sum_b w^2 over the frames covering each
+        sample, 0 where that denominator is <= 1e-11.  Bit-identical from call to call."""
+        n = self.size
+        bins = n // 2 + 1
+        for t, name in ((re, "re"), (im, "im")):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2:
+                raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be a 2-D tensor [frames, N/2 + 1]")
+            self._check(t, name, last=bins)
+        if re.shape != im.shape:
+            raise PdspError(_capi.ERR_BAD_ARG, f"re {tuple(re.shape)} and im {tuple(im.shape)} differ in shape")
+        frames = re.shape[0]
+        if frames < 1:
+            raise PdspError(_capi.ERR_BAD_ARG, "frames must be >= 1, got 0")
+        if int(hop) < 1:
+            raise PdspError(_capi.ERR_BAD_ARG, f"hop must be >= 1, got {hop}")
+        win = self._table_window(window)
+        total = (frames - 1) * int(hop) + n
+        if out is None:
+            out = torch.empty((total,), dtype=self.dtype, device=self.device)
+        else:
+            if not isinstance(out, torch.Tensor) or out.dim() != 1:
+                raise PdspError(_capi.ERR_BAD_ARG, f"out must be a 1-D tensor of {total} samples")
+            self._check(out, "out", last=total)
+        check(getattr(lib, "pdsp_istft_" + self._sfx)(self._h, frames, _ptr(re), _ptr(im), int(hop), _ptr(win), _ptr(out),
+                                                      _stream_ptr(self.device)))
+        return out
+
     def spectrum_peaks(self, frames: torch.Tensor, window="rect", sides: str = "one", sample_rate: float = 1.0,
                        want_amp: bool = False, want_phase: bool = False):
         """Rows of the whole spectrum() tail on the device: one SpectrumPeak per frame

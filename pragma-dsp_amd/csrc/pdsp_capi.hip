@@ -13,6 +13,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <climits>
 #include <cstring>
 #include <atomic>
 #include <map>
@@ -1603,5 +1604,180 @@ int pdsp_fir_filter_host_f64(const double *x, long long batch, long long len, co
   if (int rc = fir_filter_t<double>(cp.plan, batch, dx, len, len, dh, dh + bins, ntaps, y_off, y_len, dy, y_len, nullptr))
     return rc;
   PDSP_HIP_TRY(hipMemcpy(y, dy, ny * sizeof(double), hipMemcpyDeviceToHost));
+  return PDSP_OK;
+}
+
+/* ---- short-time transform (complex bins) and its overlap-add inverse -------- */
+
+namespace pdsp_host {
+
+// The short-time pair runs on the packed-real tables (N = 64 ... 16384 in both precisions), as FIR filtering.
+template <typename T>
+int check_stft_plan(const pdsp_plan *plan) {
+  if (!plan) return fail(PDSP_ERR_BAD_ARG, "plan is null");
+  if (plan->log2n < 6 || plan->log2n > pdsp::kMaxLog2N_f32 || !tables<T>(plan).tw_half || !tables<T>(plan).twr)
+    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "STFT needs a plan of 64 <= N <= 16384, got %lld", plan->n);
+  return PDSP_OK;
+}
+
+inline bool bytes_meet(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+  const char *ca = (const char *)a, *cb = (const char *)b;
+  return b && a && ca < cb + b_bytes && cb < ca + a_bytes;
+}
+
+template <typename T>
+int stft_complex_t(const pdsp_plan *plan, long long batch, const T *frames, long long frame_len, long long frame_stride,
+                   const T *window, T *re_out, T *im_out, hipStream_t s) {
+  if (int rc = check_stft_plan<T>(plan)) return rc;
+  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "frames must be >= 1, got %lld", batch);
+  if (frame_len < 1) return fail(PDSP_ERR_BAD_ARG, "frame_len must be >= 1, got %lld", frame_len);
+  if (frame_stride < 1) return fail(PDSP_ERR_BAD_ARG, "frame_stride (hop) must be >= 1, got %lld", frame_stride);
+  if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+  const long long n = plan->n, bins = n / 2 + 1, used = frame_len < n ? frame_len : n;
+  long long in_count = 0, out_count = 0;
+  if (!mad_ok(batch - 1, frame_stride, used, &in_count) || !mad_ok(batch, bins, 0, &out_count) ||
+      in_count > (LLONG_MAX / 8) || out_count > (LLONG_MAX / 8))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (!frames || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  const size_t ib = (size_t)in_count * sizeof(T), ob = (size_t)out_count * sizeof(T), wb = (size_t)n * sizeof(T);
+  if (bytes_meet(re_out, ob, frames, ib) || bytes_meet(im_out, ob, frames, ib) || bytes_meet(re_out, ob, im_out, ob) ||
+      bytes_meet(re_out, ob, window, wb) || bytes_meet(im_out, ob, window, wb))
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
+  DeviceGuard g(plan->device);
+  PDSP_HIP_TRY(g.err);
+  return stft_complex_dev<T>(plan, batch, frames, used, frame_stride, window, re_out, im_out, s);
+}
+
+template <typename T>
+int istft_t(const pdsp_plan *plan, long long frames, const T *re_in, const T *im_in, long long hop, const T *window, T *out,
+            hipStream_t s) {
+  if (int rc = check_stft_plan<T>(plan)) return rc;
+  if (frames < 1) return fail(PDSP_ERR_BAD_ARG, "frames must be >= 1, got %lld", frames);
+  if (hop < 1) return fail(PDSP_ERR_BAD_ARG, "hop must be >= 1, got %lld", hop);
+  if (frames > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", frames);
+  const long long n = plan->n, bins = n / 2 + 1;
+  long long total = 0, in_count = 0;
+  if (!mad_ok(frames - 1, hop, n, &total) || !mad_ok(frames, bins, 0, &in_count) || total > (LLONG_MAX / 8) ||
+      in_count > (LLONG_MAX / 8))
+    return fail(PDSP_ERR_BAD_ARG, "frames %lld x hop %lld overflows", frames, hop);
+  if (!re_in || !im_in || !out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  const size_t ib = (size_t)in_count * sizeof(T), ob = (size_t)total * sizeof(T), wb = (size_t)n * sizeof(T);
+  if (bytes_meet(out, ob, re_in, ib) || bytes_meet(out, ob, im_in, ib) || bytes_meet(out, ob, window, wb))
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
+  DeviceGuard g(plan->device);
+  PDSP_HIP_TRY(g.err);
+  return istft_dev<T>(plan, frames, re_in, im_in, hop, window, out, s);
+}
+
+// Host forms: size, range and window type in the order of the device forms; the plan and its window come from the
+// host entry points' plan cache.
+int stft_host_checks(long long fft_size, long long hop, int window_type) {
+  if (!pdsp_is_pow2(fft_size)) return fail(PDSP_ERR_SIZE_NOT_POW2, "FFT size must be power of two, got %lld", fft_size);
+  if (fft_size < 64 || fft_size > 16384)
+    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "STFT needs a plan of 64 <= N <= 16384, got %lld", fft_size);
+  if (hop < 1) return fail(PDSP_ERR_BAD_ARG, "hop must be >= 1, got %lld", hop);
+  if (window_type < PDSP_WIN_RECT || window_type > PDSP_WIN_BLACKMAN)
+    return fail(PDSP_ERR_WINDOW_TYPE, "Unsupported window type: %d", window_type);
+  return PDSP_OK;
+}
+
+struct HostDeviceBuf {
+  double *d = nullptr;
+  ~HostDeviceBuf() {
+    if (d) (void)hipFree(d);
+  }
+};
+
+}  // namespace pdsp_host
+
+int pdsp_stft_complex_f32(const pdsp_plan *plan, long long batch, const float *frames, long long frame_len,
+                          long long frame_stride, const float *window, float *re_out, float *im_out, pdsp_stream stream) {
+  return stft_complex_t<float>(plan, batch, frames, frame_len, frame_stride, window, re_out, im_out, (hipStream_t)stream);
+}
+int pdsp_stft_complex_f64(const pdsp_plan *plan, long long batch, const double *frames, long long frame_len,
+                          long long frame_stride, const double *window, double *re_out, double *im_out,
+                          pdsp_stream stream) {
+  return stft_complex_t<double>(plan, batch, frames, frame_len, frame_stride, window, re_out, im_out, (hipStream_t)stream);
+}
+int pdsp_istft_f32(const pdsp_plan *plan, long long frames, const float *re_in, const float *im_in, long long hop,
+                   const float *window, float *out, pdsp_stream stream) {
+  return istft_t<float>(plan, frames, re_in, im_in, hop, window, out, (hipStream_t)stream);
+}
+int pdsp_istft_f64(const pdsp_plan *plan, long long frames, const double *re_in, const double *im_in, long long hop,
+                   const double *window, double *out, pdsp_stream stream) {
+  return istft_t<double>(plan, frames, re_in, im_in, hop, window, out, (hipStream_t)stream);
+}
+
+int pdsp_set_istft_chunk_frames(int frames) {
+  const int prev = g_istft_chunk_frames;
+  g_istft_chunk_frames = frames > 0 ? frames : 0;
+  return prev;
+}
+
+int pdsp_stft_host_f64(const double *signal, long long len, long long fft_size, long long hop, int window_type,
+                       double *re_out, double *im_out) {
+  if (int rc = stft_host_checks(fft_size, hop, window_type)) return rc;
+  if (len < fft_size)
+    return fail(PDSP_ERR_INPUT_LENGTH, "signal length %lld is shorter than one frame (%lld)", len, fft_size);
+  const long long frames = 1 + (len - fft_size) / hop, bins = fft_size / 2 + 1;
+  if (frames > 0x7fffffffLL || len > (1LL << 40)) return fail(PDSP_ERR_BAD_ARG, "signal too long: %lld samples", len);
+  if (!signal || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  if (int rc = require_device()) return rc;
+  CachedPlan cp;
+  if (int rc = cached_plan(fft_size, &cp)) return rc;
+  pdsp_plan *const plan = cp.plan;
+  std::lock_guard<std::mutex> lk(plan->mu);
+  DeviceGuard g(plan->device);
+  PDSP_HIP_TRY(g.err);
+  const double *win = nullptr;
+  if (window_type != PDSP_WIN_RECT)
+    if (int rc = plan_window<double>(plan, window_type, &win)) return rc;
+  if (!plan->stream) PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
+  const hipStream_t s = plan->stream;
+  const size_t nx = (size_t)len, ny = (size_t)(frames * bins);
+  HostDeviceBuf sc;
+  PDSP_HIP_TRY(hipMalloc((void **)&sc.d, (nx + 2 * ny) * sizeof(double)));
+  double *dx = sc.d, *dre = sc.d + nx, *dim = dre + ny;
+  PDSP_HIP_TRY(hipMemcpyAsync(dx, signal, nx * sizeof(double), hipMemcpyHostToDevice, s));
+  if (int rc = stft_complex_t<double>(plan, frames, dx, fft_size, hop, win, dre, dim, s)) return rc;
+  PDSP_HIP_TRY(hipStreamSynchronize(s));
+  PDSP_HIP_TRY(hipMemcpy(re_out, dre, ny * sizeof(double), hipMemcpyDeviceToHost));
+  PDSP_HIP_TRY(hipMemcpy(im_out, dim, ny * sizeof(double), hipMemcpyDeviceToHost));
+  return PDSP_OK;
+}
+
+int pdsp_istft_host_f64(const double *re, const double *im, long long frames, long long fft_size, long long hop,
+                        int window_type, double *out) {
+  if (int rc = stft_host_checks(fft_size, hop, window_type)) return rc;
+  if (frames < 1) return fail(PDSP_ERR_BAD_ARG, "frames must be >= 1, got %lld", frames);
+  const long long bins = fft_size / 2 + 1;
+  long long total = 0, in_count = 0;
+  if (frames > 0x7fffffffLL || !mad_ok(frames - 1, hop, fft_size, &total) || !mad_ok(frames, bins, 0, &in_count) ||
+      total > (1LL << 40) || in_count > (1LL << 40))
+    return fail(PDSP_ERR_BAD_ARG, "frames %lld x hop %lld overflows", frames, hop);
+  if (!re || !im || !out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  if (int rc = require_device()) return rc;
+  CachedPlan cp;
+  if (int rc = cached_plan(fft_size, &cp)) return rc;
+  pdsp_plan *const plan = cp.plan;
+  std::lock_guard<std::mutex> lk(plan->mu);
+  DeviceGuard g(plan->device);
+  PDSP_HIP_TRY(g.err);
+  const double *win = nullptr;
+  if (window_type != PDSP_WIN_RECT)
+    if (int rc = plan_window<double>(plan, window_type, &win)) return rc;
+  // the plan's own stream, synchronised before the results are copied out: the two-pass inverse draws its scratch
+  // stream-ordered (StreamScratch), so every step of the call is ordered on one explicit stream
+  if (!plan->stream) PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
+  const hipStream_t s = plan->stream;
+  const size_t nin = (size_t)in_count, ny = (size_t)total;
+  HostDeviceBuf sc;
+  PDSP_HIP_TRY(hipMalloc((void **)&sc.d, (2 * nin + ny) * sizeof(double)));
+  double *dre = sc.d, *dim = sc.d + nin, *dy = dim + nin;
+  PDSP_HIP_TRY(hipMemcpyAsync(dre, re, nin * sizeof(double), hipMemcpyHostToDevice, s));
+  PDSP_HIP_TRY(hipMemcpyAsync(dim, im, nin * sizeof(double), hipMemcpyHostToDevice, s));
+  if (int rc = istft_t<double>(plan, frames, dre, dim, hop, win, dy, s)) return rc;
+  PDSP_HIP_TRY(hipStreamSynchronize(s));
+  PDSP_HIP_TRY(hipMemcpy(out, dy, ny * sizeof(double), hipMemcpyDeviceToHost));
   return PDSP_OK;
 }

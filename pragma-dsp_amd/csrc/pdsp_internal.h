@@ -1,6 +1,6 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from five translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from six translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
@@ -8,6 +8,7 @@
 //   pdsp_kernels_f32_spectrum.hip spectrum_impl<float> (fused spectrum kernels, findPeak kernels)
 //   pdsp_kernels_f64.hip          every dispatcher for double
 //   pdsp_kernels_fir.hip          FIR filtering (fused overlap-save) and the filter spectrum, f32 and f64
+//   pdsp_kernels_stft.hip         complex STFT and its overlap-add inverse, f32 and f64
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -260,5 +261,18 @@ int fir_filter_dev(const pdsp_plan *plan, long long batch, const T *x, long long
                    long long nblk, hipStream_t s);
 template <typename T>
 int fir_spectrum_dev(const pdsp_plan *plan, const T *taps, int ntaps, T *h_re, T *h_im, hipStream_t s);
+
+// pdsp_stft_complex_* / pdsp_istft_* after validation (pdsp_kernels_stft.hip): 64 <= N <= 16384, frames >= 1,
+// 1 <= frame_len <= N, hop >= 1; window null (rect) or N values
+extern int g_istft_chunk_frames;  // pdsp_set_istft_chunk_frames: frames per chunk of the two-pass inverse (0: default)
+template <typename T>
+int stft_complex_dev(const pdsp_plan *plan, long long batch, const T *frames, long long frame_len,
+                     long long frame_stride, const T *window, T *re_out, T *im_out, hipStream_t s);
+template <typename T>
+int istft_dev(const pdsp_plan *plan, long long frames, const T *re_in, const T *im_in, long long hop, const T *window,
+              T *out, hipStream_t s);
+// bytes of stream-ordered scratch istft_dev draws (0 when hop >= N)
+template <typename T>
+size_t istft_scratch_bytes(long long n, long long hop, long long frames);
 
 }  // namespace pdsp_host

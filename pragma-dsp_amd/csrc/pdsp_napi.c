@@ -564,6 +564,57 @@ static napi_value FirFilter(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* stft(signal, fftSize, hopSize, windowType, real, imag): real / imag receive F x (fftSize/2 + 1) bins,
+ * F = 1 + (len - fftSize) / hopSize.  fftSize and hopSize are bounded before any multiply; arguments the library
+ * refuses reach it unchanged (it fails before touching the outputs), so its message is what the caller sees. */
+static napi_value Stft(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return NULL;
+  double *x, *re, *im;
+  size_t nx, nre, nim;
+  int64_t n, hop, win;
+  if (!f64_array(env, argv[0], &x, &nx) || !get_i64(env, argv[1], &n) || !get_i64(env, argv[2], &hop) ||
+      !get_i64(env, argv[3], &win) || !f64_array(env, argv[4], &re, &nre) || !f64_array(env, argv[5], &im, &nim))
+    return NULL;
+  if (n >= 64 && n <= 16384 && hop >= 1 && (int64_t)nx >= n) {
+    const int64_t frames = 1 + ((int64_t)nx - n) / hop, need = frames * (n / 2 + 1);  /* nx < 2^53, bins <= 8193 */
+    if ((int64_t)nre < need || (int64_t)nim < need) {
+      napi_throw_error(env, NULL, "pdsp_napi: stft output too small");
+      return NULL;
+    }
+  }
+  if (pdsp_stft_host_f64(x, (long long)nx, (long long)n, (long long)hop, (int)win, re, im) != PDSP_OK) return throw_pdsp(env);
+  return NULL;
+}
+
+/* istft(real, imag, frames, fftSize, hopSize, windowType, out): out receives (frames - 1) hopSize + fftSize samples. */
+static napi_value Istft(napi_env env, napi_callback_info info) {
+  napi_value argv[7];
+  if (!get_args(env, info, 7, argv)) return NULL;
+  double *re, *im, *y;
+  size_t nre, nim, ny;
+  int64_t frames, n, hop, win;
+  if (!f64_array(env, argv[0], &re, &nre) || !f64_array(env, argv[1], &im, &nim) || !get_i64(env, argv[2], &frames) ||
+      !get_i64(env, argv[3], &n) || !get_i64(env, argv[4], &hop) || !get_i64(env, argv[5], &win) ||
+      !f64_array(env, argv[6], &y, &ny))
+    return NULL;
+  if (n >= 64 && n <= 16384 && hop >= 1 && frames >= 1) {
+    /* an extent that overflows, or exceeds the library's 2^40 bound, goes to the library, which refuses it */
+    int64_t need_in = 0, need_out = 0;
+    const int overflow = __builtin_mul_overflow(frames, n / 2 + 1, &need_in) ||
+                         __builtin_mul_overflow(frames - 1, hop, &need_out) ||
+                         __builtin_add_overflow(need_out, n, &need_out) || need_in > ((int64_t)1 << 40) ||
+                         need_out > ((int64_t)1 << 40);
+    if (!overflow && ((int64_t)nre < need_in || (int64_t)nim < need_in || (int64_t)ny < need_out)) {
+      napi_throw_error(env, NULL, "pdsp_napi: istft buffers too small");
+      return NULL;
+    }
+  }
+  if (pdsp_istft_host_f64(re, im, (long long)frames, (long long)n, (long long)hop, (int)win, y) != PDSP_OK)
+    return throw_pdsp(env);
+  return NULL;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   const struct {
     const char *name;
@@ -575,7 +626,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"spectrum", Spectrum},     {"binFrequencies", BinFrequencies}, {"fftShift", FftShift},
       {"spectrumBatch", SpectrumBatch}, {"spectrumRows", SpectrumRows},
       {"nextPow2", NextPow2},     {"deviceCount", DeviceCount},
-      {"firFilter", FirFilter},
+      {"firFilter", FirFilter},   {"stft", Stft},               {"istft", Istft},
   };
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
     napi_value f;

@@ -2,11 +2,13 @@
 import * as coreNs from './core';
 import * as fourierNs from './fourier';
 import * as filtersNs from './filters';
+import * as stftNs from './stft';
 
 export { spectrum, spectrumBatch, spectrumStream, SpectrumOptions, SpectrumPeak, SpectrumResult } from './spectrum';
 export { ComplexArray } from './core';
 export { WindowType } from './fourier';
 export { FirMode, FirFilterOptions } from './filters';
+export { StftWindow, StftOptions, StftResult } from './stft';
 
 export const core: {
   createComplexArray: typeof coreNs.createComplexArray;
@@ -26,4 +28,8 @@ export const fourier: {
 };
 export const filters: {
   firFilter: typeof filtersNs.firFilter;
+};
+export const stft: {
+  stft: typeof stftNs.stft;
+  istft: typeof stftNs.istft;
 };

@@ -4,10 +4,12 @@
 //   require('.../js').core       -> pragma-dsp/core
 //   require('.../js').fourier    -> pragma-dsp/xform/fourier
 //   require('.../js').filters    -> pragma-dsp/filters (ROADMAP.md, "Filters and utilities")
+//   require('.../js').stft       -> pragma-dsp/xform/stft (ROADMAP.md, "A) STFT")
 const core = require('./core');
 const fourier = require('./fourier');
 const s = require('./spectrum');
 const filters = require('./filters');
+const stft = require('./stft');
 
 module.exports = {
   spectrum: s.spectrum,
@@ -34,5 +36,10 @@ module.exports = {
 // `.filters` but not enumerated, so that the key list of the reference's three surfaces stays exactly theirs.
 Object.defineProperty(module.exports, 'filters', {
   value: { firFilter: filters.firFilter },
+  enumerable: false,
+});
+// pragma-dsp/xform/stft: planned by the reference (ROADMAP.md, "A) STFT"), not enumerated for the same reason.
+Object.defineProperty(module.exports, 'stft', {
+  value: { stft: stft.stft, istft: stft.istft },
   enumerable: false,
 });
