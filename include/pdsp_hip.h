@@ -204,7 +204,10 @@ PDSP_API int pdsp_fft_inverse_f32(const pdsp_plan *plan, long long batch,
 PDSP_API int pdsp_apply_window_f32(long long batch, long long n, const float *in,
                                    const float *window, float *out, pdsp_stream stream);
 /* magnitude, src/xform/fourier.ts:98-109 (sqrt(re^2+im^2) in f32; not the
- * overflow-safe hypot: fine for |X| < 1e19). */
+ * overflow-safe hypot).  Within 1 ulp while re^2 + im^2 is a normal f32:
+ * 1.1e-19 <= |X| <= 1.8e19.  The fused amplitude stores of pdsp_spectrum_f32 /
+ * pdsp_spectrum_peaks_f32 square either the bin or half its scaled amplitude, so
+ * their rows hold for |X_k| <= 1.8e19 and amplitudes >= 2.2e-19; see DESIGN.md §1. */
 PDSP_API int pdsp_magnitude_f32(long long count, const float *re, const float *im,
                                 float *out, pdsp_stream stream);
 /* phase, src/xform/fourier.ts:111-120: atan2(im, re). */
