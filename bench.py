@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the headline metric of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input that is
 already resident in HBM: by default BASELINE.json configs[2], the roofline run
@@ -15,19 +15,22 @@ collective (weak scaling: 65,536 transforms per GPU, configs[4] at N=8 -- the ba
 of bench/reallife/signals.ts:264-270 generalised), and the timed region is bracketed by
 a barrier + synchronize with the MAX over ranks taken.  Rank 0 prints ONE JSON line.
 The control plane (barriers, the MAX, per-rank read-outs: host scalars) runs over gloo on loopback;
-RCCL carries the path's one exchange step, which at N > 1 follows the timed region and is
-timed on its own (`--no-gather` skips it): the all-gather over xGMI of the 16-byte-per-frame SpectrumPeak
+RCCL carries the path's one exchange step, which at N > 1 with `--full` (or `--gather`) follows the
+timed region and is timed on its own (`--no-gather` skips it): the all-gather over xGMI of the 16-byte-per-frame SpectrumPeak
 records and of the output slabs, under a watchdog (`--gather-timeout`) -- a failed exchange is reported in
 the line (status 0), a HUNG one is abandoned: the line is printed, every rank exits 5; the measured value
 stands either way.  `--rccl-selftest` runs that leg in a world of ONE rank on one card (a real RCCL group).
 
-The default line (N = 1, no flags) also carries, outside the headline's timed region: `parity` (256 rows of the
-timed output vs the CPU oracle), `roofline.traffic` measured by two child runs under rocprofv3 --pmc,
+A plain run does only what the headline needs: it sets up, ramps the clocks and warms up, times the steps, writes
+`--dump-outputs` if asked, and prints the line (`roofline` from the timed steps, `roofline.traffic` quoted from the
+committed profiles/traffic.json, `clocks`: sclk / board power under load).  Everything else it can measure or check
+runs only with `--full`, after the timed region: `parity` (256 rows of the timed output vs the CPU oracle),
+`cpu_baseline` (the oracle and its Node restatement on one host core), `roofline.device_copy_same_buffers_GBps`,
+and, on the default line (N = 1), `roofline.traffic` measured by two child runs under rocprofv3 --pmc,
 `also.spectrum16k` (configs[3] at its stated size: the whole 2^20-frame stream resident in HBM, its own parity and
 CPU baseline), `also.fft4096_f64` (the headline shape in the reference's own precision), `also.single1024`
-(configs[1]: one N=1024 frame through the drop-in, microseconds, beside the Node CPU path), `cpu_baseline` (the oracle
-and its Node restatement on one host core), `clocks` (sclk / board power under load).  A failed parity check
-makes the run exit 4.
+(configs[1]: one N=1024 frame through the drop-in, microseconds, beside the Node CPU path), `also.placement`,
+`also.real4096`, `also.hostbatch4096`; at N > 1 the exchange leg.  A failed parity check makes the run exit 4.
 
 Other workloads (parity-checked elsewhere; here for DESIGN.md's numbers):
   --workload spectrum16k   configs[3]: fused Hann+FFT+one-sided amplitude, N=16384,
@@ -593,8 +596,13 @@ def parse_args(argv):
     ap.add_argument("--batch", type=int, default=None, help="transforms per GPU (default: the config's)")
     ap.add_argument("--n", type=int, default=None, help="spectrum256 only: another frame size (development sweeps)")
     ap.add_argument("--chunk", type=int, default=16384, help="frames per launch for spectrum16k")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (oracle baseline + parity rows)")
-    ap.add_argument("--no-also", action="store_true", help="skip the configs[3] and f64 legs attached to the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run what the headline does not need: parity rows and CPU "
+                         "baselines, the device-copy yardstick, the also.* legs and the measured roofline.traffic of the "
+                         "default line, the exchange leg at N > 1 (a plain run skips all of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU legs (oracle baseline + parity rows)")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the also.* legs attached to the default line")
     ap.add_argument("--also-reuse-chunk", action="store_true",
                     help="the configs[3] leg re-reads one 1-GiB chunk instead of keeping the whole 96-GiB stream resident")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -603,13 +611,14 @@ def parse_args(argv):
                     help="backend of the exchange leg: nccl (= RCCL, default) or gloo (default with --share-gpu / --dry-run); "
                          "the control plane is always gloo")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0")
-    ap.add_argument("--gather", action="store_true", help="(default at --gpus > 1; kept for older command lines)")
+    ap.add_argument("--gather", action="store_true",
+                    help="N > 1: run the exchange leg without the rest of --full (with --full it runs by default)")
     ap.add_argument("--no-gather", action="store_true",
                     help="N > 1: skip the RCCL all-gather of the output slabs and of the peak records (timed on its own, after the timed region)")
     ap.add_argument("--measure-traffic", action="store_true",
                     help="N = 1: measure roofline.traffic in this run -- two child runs of this workload under "
                          "`rocprofv3 --pmc` (FETCH_SIZE, WRITE_SIZE; ~20 s) -- instead of quoting profiles/traffic.json; "
-                         "default for the default workload unless this process itself runs under a profiler")
+                         "default with --full for the default workload unless this process itself runs under a profiler")
     ap.add_argument("--no-measure-traffic", action="store_true", help="quote profiles/traffic.json (the committed PMC pass)")
     ap.add_argument("--gather-timeout", type=float, default=150.0,
                     help="N > 1: seconds the exchange leg may take before the line is printed without it")
@@ -633,10 +642,12 @@ def parse_args(argv):
     if args.dump_outputs is not None and (args.dry_run or args.workload in ("single1024", "stream", "hostbatch")):
         ap.error("--dump-outputs needs one of the batched workloads (fft4096, fft4096_f64, real4096, fft16k, spectrum16k, "
                  "spectrum256, peaks16k) and no --dry-run")
+    if not args.full:  # a plain run: the headline and nothing else
+        args.no_cpu_baseline = args.no_also = True
     under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
     if args.no_measure_traffic or under_profiler or os.environ.get("PDSP_BENCH_PMC_CHILD"):
         args.measure_traffic = False
-    elif args.workload == "fft4096" and args.batch is None and args.gpus == 1 and "WORLD_SIZE" not in os.environ:
+    elif args.full and args.workload == "fft4096" and args.batch is None and args.gpus == 1 and "WORLD_SIZE" not in os.environ:
         args.measure_traffic = True
     if args.dist_backend is None:
         args.dist_backend = "gloo" if (args.share_gpu or args.dry_run) else "nccl"
@@ -888,10 +899,10 @@ def run_rank(args, world: int, rank: int, local: int) -> int:
         dist.all_gather(allms, t)
         per_rank_ms = [float(x.item()) for x in allms]
 
-    # context for the roofline fraction (outside the timed region): the rate at which this box, with
+    # context for the roofline fraction (outside the timed region, --full): the rate at which this card, with
     # these very buffers, copies the input planes to the output planes (torch's device copy kernel)
     copy_gbps, copy_clocks = None, None
-    if args.workload in ("fft4096", "fft16k", "fft4096_f64") and rank == 0 and world == 1:
+    if args.full and args.workload in ("fft4096", "fft16k", "fft4096_f64") and rank == 0 and world == 1:
         for _ in range(3):
             ore.copy_(re)
             oim.copy_(im)
@@ -1025,7 +1036,8 @@ def run_rank(args, world: int, rank: int, local: int) -> int:
     # The one exchange step of the path, timed on its own AFTER the line is assembled: the value is
     # already measured, so neither a failed nor a hung exchange may take it away (exchange_leg below).
     gather = None
-    if (world > 1 or args.rccl_selftest) and not args.no_gather and args.workload in ("fft4096", "real4096"):
+    wants_gather = args.rccl_selftest or (world > 1 and (args.full or args.gather))
+    if wants_gather and not args.no_gather and args.workload in ("fft4096", "real4096"):
         gather = exchange_leg(args, world, rank, dev, plan, re, ore, oim, per_gpu, out, barrier)
 
     if rank == 0:

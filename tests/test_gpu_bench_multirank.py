@@ -1,6 +1,6 @@
 """bench.py's N > 1 path and its RCCL leg, as far as ONE card can run them: the exchange leg in a
 world of one rank over a real RCCL group (`--rccl-selftest`), and two ranks sharing the card with real compute and
-the gloo exchange (`--gpus 2 --share-gpu`), in the self-launching form.  Small batches: these are plumbing checks of
+the gloo exchange and parity (`--gpus 2 --share-gpu --full`), in the self-launching form.  Small batches: these are plumbing checks of
 statuses, fields and teardown, not measurements."""
 import json
 import os
@@ -45,7 +45,7 @@ def test_rccl_selftest_one_rank_group_on_this_card():
 
 
 def test_two_ranks_sharing_the_card_gloo_exchange_and_parity():
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--share-gpu"] + QUICK, capture_output=True, text=True,
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--share-gpu", "--full"] + QUICK, capture_output=True, text=True,
                        timeout=900, env=_env(), cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p)

@@ -8,8 +8,8 @@
 REPO=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$REPO/${1:-gpurun_out/rehearsal}
 mkdir -p "$OUT"; cd "$REPO"
-timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --share-gpu > "$OUT/torchrun_share2_gloo.json" 2> "$OUT/torchrun_share2_gloo.err"; echo "rc torchrun/gloo = $?"
-timeout -k 10 300 python bench.py --gpus 2 --steps 5 --warmup 2 --share-gpu --dist-backend nccl --no-cpu-baseline --gather-timeout 60 > "$OUT/self_share2_rccl_refused.json" 2> "$OUT/self_share2_rccl_refused.err"; echo "rc self/rccl-on-one-card = $?"
+timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --share-gpu --full > "$OUT/torchrun_share2_gloo.json" 2> "$OUT/torchrun_share2_gloo.err"; echo "rc torchrun/gloo = $?"
+timeout -k 10 300 python bench.py --gpus 2 --steps 5 --warmup 2 --share-gpu --full --dist-backend nccl --no-cpu-baseline --gather-timeout 60 > "$OUT/self_share2_rccl_refused.json" 2> "$OUT/self_share2_rccl_refused.err"; echo "rc self/rccl-on-one-card = $?"
 timeout -k 10 300 python bench.py --rccl-selftest --steps 5 --warmup 2 --no-measure-traffic --no-also --no-cpu-baseline > "$OUT/rccl_selftest.json" 2> "$OUT/rccl_selftest.err"; echo "rc rccl-selftest = $?"
 python - "$OUT" <<'PY'
 import json, sys
