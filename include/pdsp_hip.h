@@ -454,6 +454,28 @@ PDSP_API int pdsp_stft_host_f64(const double *signal, long long len, long long f
 PDSP_API int pdsp_istft_host_f64(const double *re, const double *im, long long frames, long long fft_size,
                                  long long hop, int window_type, double *out);
 
+/* ---- discrete cosine transform, types 2 and 3, f32 / f64 ------------------------------------- */
+/* The reference's roadmap v0.3 (ROADMAP.md: pragma-dsp/xform/dct, dct(signal, { type }), idct(...)).  Conventions
+ * are scipy.fft.dct's:
+ *   type 2:  y[k] = 2 sum_n x[n] cos(pi k (2n + 1) / (2N))
+ *   type 3:  y[k] = x[0] + 2 sum_{n >= 1} x[n] cos(pi n (2k + 1) / (2N))
+ * norm BACKWARD scales by 1, FORWARD by 1/(2N), ORTHO makes the transform orthonormal (type 2: y[0] / sqrt(4N),
+ * y[k] / sqrt(2N); type 3: the backward transform of x[0] / sqrt(N), x[n] / sqrt(2N)).  The inverses follow:
+ * scipy.fft.idct(x, type t, norm n) == dct(x, type 5 - t, norm n with BACKWARD and FORWARD exchanged).
+ * N = pdsp_plan_size(), 64 <= N <= 16384 in both precisions (any other power of two: PDSP_ERR_UNSUPPORTED_SIZE).
+ * One launch, N values in and N values out per row; f32 ~1e-7 * log2 N of max|y|, f64 ~1e-16 * log2 N.
+ * Every argument is checked before any device work: a null plan or buffer, batch < 1, a stride < N, a type other
+ * than 2 or 3, an unknown norm, extents that overflow 64 bits or a grid of 2^31 rows give PDSP_ERR_BAD_ARG, and so
+ * does an output whose byte extent meets the input's, except the exact in-place call y == x, y_stride == x_stride. */
+typedef enum pdsp_dct_norm { PDSP_DCT_BACKWARD = 0, PDSP_DCT_ORTHO = 1, PDSP_DCT_FORWARD = 2 } pdsp_dct_norm;
+/* y = scipy.fft.dct(x, type, norm) per row; `batch` rows at x_stride / y_stride >= N elements */
+PDSP_API int pdsp_dct_f32(const pdsp_plan *plan, long long batch, const float *x, long long x_stride, int type,
+                          int norm, float *y, long long y_stride, pdsp_stream stream);
+PDSP_API int pdsp_dct_f64(const pdsp_plan *plan, long long batch, const double *x, long long x_stride, int type,
+                          int norm, double *y, long long y_stride, pdsp_stream stream);
+/* synchronous f64 host form: `batch` contiguous rows of n values (n a power of two, 64 ... 16384) */
+PDSP_API int pdsp_dct_host_f64(const double *x, long long batch, long long n, int type, int norm, double *y);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ ERR_DEVICE = 10
 WINDOW_TYPES = {"rect": 0, "hann": 1, "hamming": 2, "blackman": 3}
 SIDES = {"one": 0, "two": 1}
 FIR_MODES = {"full": 0, "same": 1, "valid": 2, "filter": 3}
+DCT_NORMS = {"backward": 0, "ortho": 1, "forward": 2}
 COMPLEX_OPS = {"add": 0, "sub": 1, "mul": 2, "div": 3, "conj": 4, "scale": 5, "mulScalar": 6}
 
 
@@ -134,6 +135,9 @@ def _load() -> C.CDLL:
         "pdsp_stft_host_f64": ([dp, ll, ll, ll, i32, dp, dp], i32),
         "pdsp_istft_host_f64": ([dp, dp, ll, ll, ll, i32, dp], i32),
         "pdsp_set_istft_chunk_frames": ([i32], i32),
+        "pdsp_dct_f32": ([vp, ll, vp, ll, i32, i32, vp, ll, vp], i32),
+        "pdsp_dct_f64": ([vp, ll, vp, ll, i32, i32, vp, ll, vp], i32),
+        "pdsp_dct_host_f64": ([dp, ll, ll, i32, i32, dp], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -341,6 +341,60 @@ class BatchedFft:
                                                       _stream_ptr(self.device)))
         return out
 
+    def _dct_call(self, x, type, norm, out, name):
+        """Validation shared by dct / idct: x [rows, N] with contiguous rows at any row stride >= N (x.stride(0));
+        out None, x itself (exact in place) or a tensor of the same shape with its own row stride."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise PdspError(_capi.ERR_BAD_ARG, f"{name}: x must be a 2-D tensor [rows, N]")
+        n = self.size
+        for t, tn in ((x, "x"), (out, "out")):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dim() != 2:
+                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: {tn} must be a 2-D tensor [rows, N]")
+            if t.dtype != self.dtype or not t.is_cuda or t.device != self.device:
+                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: {tn} must be a {self.dtype} tensor on {self.device}")
+            if t.shape[-1] != n:
+                raise PdspError(_capi.ERR_INPUT_LENGTH, f"FFT input length {t.shape[-1]} != size {n}")
+            if t.shape[0] > 1 and t.stride(0) < n or t.stride(1) != 1:
+                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: {tn} needs contiguous rows at a row stride >= N")
+        if out is not None and out.shape != x.shape:
+            raise PdspError(_capi.ERR_BAD_ARG, f"{name}: out {tuple(out.shape)} and x {tuple(x.shape)} differ in shape")
+        if type not in (2, 3):
+            raise PdspError(_capi.ERR_BAD_ARG, f"DCT type must be 2 or 3, got {type}")
+        if norm is None:
+            norm = "backward"
+        if norm not in _capi.DCT_NORMS:
+            raise PdspError(_capi.ERR_BAD_ARG, f"DCT norm must be 'backward', 'ortho' or 'forward', got {norm!r}")
+        rows = x.shape[0]
+        if rows < 1:
+            raise PdspError(_capi.ERR_BAD_ARG, "batch must be >= 1, got 0")
+        if out is None:
+            out = torch.empty((rows, n), dtype=self.dtype, device=self.device)
+        xs = x.stride(0) if rows > 1 else n
+        ys = out.stride(0) if rows > 1 else n
+        if out.data_ptr() == x.data_ptr() and rows > 1 and ys != xs:
+            raise PdspError(_capi.ERR_BAD_ARG, "output overlaps input (only y == x with y_stride == x_stride may share bytes)")
+        if out.data_ptr() == x.data_ptr():
+            ys = xs
+        check(getattr(lib, "pdsp_dct_" + self._sfx)(self._h, rows, _ptr(x), xs, int(type), _capi.DCT_NORMS[norm],
+                                                    _ptr(out), ys, _stream_ptr(self.device)))
+        return out
+
+    def dct(self, x: torch.Tensor, type: int = 2, norm: str = "backward", out: torch.Tensor | None = None):
+        """scipy dct(x, type, norm=norm, axis=-1) of the rows of x [rows, N] (types 2 and 3; norm "backward",
+        "ortho" or "forward"), one launch.  Rows may sit at any stride >= N (x.stride(0)); out=x runs in place.
+        64 <= N <= 16384."""
+        return self._dct_call(x, type, norm, out, "dct")
+
+    def idct(self, x: torch.Tensor, type: int = 2, norm: str = "backward", out: torch.Tensor | None = None):
+        """scipy idct(x, type, norm=norm, axis=-1): the DCT of type 5 - type with backward and forward norms
+        exchanged (ortho kept), as dct()."""
+        if type not in (2, 3):
+            raise PdspError(_capi.ERR_BAD_ARG, f"DCT type must be 2 or 3, got {type}")
+        swap = {"backward": "forward", "forward": "backward", None: "forward"}
+        return self._dct_call(x, 5 - type, swap.get(norm, norm), out, "idct")
+
     def spectrum_peaks(self, frames: torch.Tensor, window="rect", sides: str = "one", sample_rate: float = 1.0,
                        want_amp: bool = False, want_phase: bool = False):
         """Rows of the whole spectrum() tail on the device: one SpectrumPeak per frame

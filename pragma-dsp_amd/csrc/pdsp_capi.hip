@@ -413,6 +413,16 @@ hipError_t upload_tables(Tables<T> &t, int log2n, long long size, bool full, boo
     if (e == hipSuccess) e = hipMemcpy(t.tw_half, twh.data(), twh.size() * sizeof(T2), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc((void **)&t.twr, twr.size() * sizeof(T2));
     if (e == hipSuccess) e = hipMemcpy(t.twr, twr.data(), twr.size() * sizeof(T2), hipMemcpyHostToDevice);
+    if (e == hipSuccess && log2n <= 14) {  // DCT twiddles W_4N^k, 0 <= k <= N/2, built in f64 and rounded once
+      std::vector<T2> tw4((size_t)(size / 2 + 1));
+      for (long long k = 0; k <= size / 2; ++k) {
+        const double angle = (-M_PI * (double)k) / (2.0 * (double)size);
+        tw4[(size_t)k].x = (T)std::cos(angle);
+        tw4[(size_t)k].y = (T)std::sin(angle);
+      }
+      e = hipMalloc((void **)&t.tw4n, tw4.size() * sizeof(T2));
+      if (e == hipSuccess) e = hipMemcpy(t.tw4n, tw4.data(), tw4.size() * sizeof(T2), hipMemcpyHostToDevice);
+    }
     if (e == hipSuccess && log2n == 14 && !t.tw12) {
       const std::vector<T2> t12 = build_twiddles<T2>(12);
       e = hipMalloc((void **)&t.tw12, t12.size() * sizeof(T2));
@@ -1779,5 +1789,106 @@ int pdsp_istft_host_f64(const double *re, const double *im, long long frames, lo
   if (int rc = istft_t<double>(plan, frames, dre, dim, hop, win, dy, s)) return rc;
   PDSP_HIP_TRY(hipStreamSynchronize(s));
   PDSP_HIP_TRY(hipMemcpy(out, dy, ny * sizeof(double), hipMemcpyDeviceToHost));
+  return PDSP_OK;
+}
+
+/* ---- discrete cosine transform, types 2 and 3 ------------------------------ */
+
+namespace pdsp_host {
+
+// The DCT runs on the packed-real tables plus W_4N^k (N = 64 ... 16384 in both precisions), as the short-time pair.
+template <typename T>
+int check_dct_plan(const pdsp_plan *plan) {
+  if (!plan) return fail(PDSP_ERR_BAD_ARG, "plan is null");
+  if (plan->log2n < 6 || plan->log2n > pdsp::kMaxLog2N_f32 || !tables<T>(plan).tw_half || !tables<T>(plan).twr ||
+      !tables<T>(plan).tw4n)
+    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "DCT needs a plan of 64 <= N <= 16384, got %lld", plan->n);
+  return PDSP_OK;
+}
+
+int check_dct_type_norm(int type, int norm) {
+  if (type != 2 && type != 3) return fail(PDSP_ERR_BAD_ARG, "DCT type must be 2 or 3, got %d", type);
+  if (norm < PDSP_DCT_BACKWARD || norm > PDSP_DCT_FORWARD)
+    return fail(PDSP_ERR_BAD_ARG, "DCT norm must be 0 (backward), 1 (ortho) or 2 (forward), got %d", norm);
+  return PDSP_OK;
+}
+
+// scipy's norm as the kernels' two scalars, computed in f64 and rounded once: g for every output (type 2) or input
+// (type 3), g0 for index 0 instead
+void dct_scales(long long n, int type, int norm, double *g, double *g0) {
+  const double nn = (double)n;
+  if (norm == PDSP_DCT_FORWARD) {
+    *g = *g0 = 1.0 / (2.0 * nn);
+  } else if (norm == PDSP_DCT_ORTHO) {
+    *g = 1.0 / std::sqrt(2.0 * nn);
+    *g0 = type == 2 ? 1.0 / std::sqrt(4.0 * nn) : 1.0 / std::sqrt(nn);
+  } else {
+    *g = *g0 = 1.0;
+  }
+}
+
+template <typename T>
+int dct_t(const pdsp_plan *plan, long long batch, const T *x, long long x_stride, int type, int norm, T *y,
+          long long y_stride, hipStream_t s) {
+  if (int rc = check_dct_plan<T>(plan)) return rc;
+  const long long n = plan->n;
+  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
+  if (x_stride < n || y_stride < n)
+    return fail(PDSP_ERR_BAD_ARG, "strides must be >= N = %lld, got x_stride %lld, y_stride %lld", n, x_stride, y_stride);
+  if (int rc = check_dct_type_norm(type, norm)) return rc;
+  long long xc = 0, yc = 0;
+  if (!mad_ok(batch - 1, x_stride, n, &xc) || !mad_ok(batch - 1, y_stride, n, &yc) || xc > (LLONG_MAX / 8) ||
+      yc > (LLONG_MAX / 8))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+  if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  // exact in place is safe (each row is loaded in full by its own workgroup before that workgroup's first barrier);
+  // any other overlap would let one row's stores reach another row's loads
+  const bool in_place = (const void *)x == (const void *)y && x_stride == y_stride;
+  if (!in_place && bytes_meet(y, (size_t)yc * sizeof(T), x, (size_t)xc * sizeof(T)))
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only y == x with y_stride == x_stride may share bytes)");
+  double g = 1.0, g0 = 1.0;
+  dct_scales(n, type, norm, &g, &g0);
+  DeviceGuard dg(plan->device);
+  PDSP_HIP_TRY(dg.err);
+  return dct_dev<T>(plan, batch, x, x_stride, type, (T)g, (T)g0, y, y_stride, s);
+}
+
+}  // namespace pdsp_host
+
+int pdsp_dct_f32(const pdsp_plan *plan, long long batch, const float *x, long long x_stride, int type, int norm,
+                 float *y, long long y_stride, pdsp_stream stream) {
+  return dct_t<float>(plan, batch, x, x_stride, type, norm, y, y_stride, (hipStream_t)stream);
+}
+int pdsp_dct_f64(const pdsp_plan *plan, long long batch, const double *x, long long x_stride, int type, int norm,
+                 double *y, long long y_stride, pdsp_stream stream) {
+  return dct_t<double>(plan, batch, x, x_stride, type, norm, y, y_stride, (hipStream_t)stream);
+}
+
+int pdsp_dct_host_f64(const double *x, long long batch, long long n, int type, int norm, double *y) {
+  if (!pdsp_is_pow2(n)) return fail(PDSP_ERR_SIZE_NOT_POW2, "FFT size must be power of two, got %lld", n);
+  if (n < 64 || n > 16384) return fail(PDSP_ERR_UNSUPPORTED_SIZE, "DCT needs a plan of 64 <= N <= 16384, got %lld", n);
+  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
+  if (int rc = check_dct_type_norm(type, norm)) return rc;
+  long long count = 0;
+  if (batch > 0x7fffffffLL || !mad_ok(batch, n, 0, &count) || count > (1LL << 40))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x %lld overflows", batch, n);
+  if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  if (int rc = require_device()) return rc;
+  CachedPlan cp;
+  if (int rc = cached_plan(n, &cp)) return rc;
+  pdsp_plan *const plan = cp.plan;
+  std::lock_guard<std::mutex> lk(plan->mu);
+  DeviceGuard g(plan->device);
+  PDSP_HIP_TRY(g.err);
+  if (!plan->stream) PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
+  const hipStream_t s = plan->stream;
+  const size_t nx = (size_t)count;
+  HostDeviceBuf sc;
+  PDSP_HIP_TRY(hipMalloc((void **)&sc.d, nx * sizeof(double)));
+  PDSP_HIP_TRY(hipMemcpyAsync(sc.d, x, nx * sizeof(double), hipMemcpyHostToDevice, s));
+  if (int rc = dct_t<double>(plan, batch, sc.d, n, type, norm, sc.d, n, s)) return rc;  // in place
+  PDSP_HIP_TRY(hipStreamSynchronize(s));
+  PDSP_HIP_TRY(hipMemcpy(y, sc.d, nx * sizeof(double), hipMemcpyDeviceToHost));
   return PDSP_OK;
 }

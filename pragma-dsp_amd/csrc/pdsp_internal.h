@@ -1,6 +1,6 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from six translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from seven translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
@@ -9,6 +9,7 @@
 //   pdsp_kernels_f64.hip          every dispatcher for double
 //   pdsp_kernels_fir.hip          FIR filtering (fused overlap-save) and the filter spectrum, f32 and f64
 //   pdsp_kernels_stft.hip         complex STFT and its overlap-add inverse, f32 and f64
+//   pdsp_kernels_dct.hip          DCT-II and DCT-III, f32 and f64
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -110,6 +111,7 @@ struct Tables {
   // split twiddles W_N^k, 0 <= k <= N/4
   T2 *tw_half = nullptr;
   T2 *twr = nullptr;
+  T2 *tw4n = nullptr;  // DCT post- / pre-twiddles W_4N^k, 0 <= k <= N/2 (same plans as twr)
   T2 *tw12 = nullptr;  // N = 16384 only: radix table of the 4096-point sub-transforms (split kernels)
   T2 *tws4 = nullptr;  // rows of 16384 points (log2n2 == 14): W_16384^k, k < 768 (fft_split4_kernel)
   T2 *tws2 = nullptr;  // rows of 8192 points (log2n2 == 13): W_8192^k, k < 256 (fft_split2_kernel; uses tw12 too)
@@ -170,6 +172,8 @@ struct Tables {
     if (tw) (void)hipFree(tw);
     if (tw_half) (void)hipFree(tw_half);
     if (twr) (void)hipFree(twr);
+    if (tw4n) (void)hipFree(tw4n);
+    tw4n = nullptr;
     for (T *&w : win) {
       if (w) (void)hipFree(w);
       w = nullptr;
@@ -274,5 +278,14 @@ int istft_dev(const pdsp_plan *plan, long long frames, const T *re_in, const T *
 // bytes of stream-ordered scratch istft_dev draws (0 when hop >= N)
 template <typename T>
 size_t istft_scratch_bytes(long long n, long long hop, long long frames);
+
+// pdsp_dct_* after validation (pdsp_kernels_dct.hip): 64 <= N <= 16384, 1 <= batch < 2^31, strides >= N, type 2 or 3;
+// every output (type 2) or input (type 3) scaled by g, index 0 by g0 instead.  y == x with y_stride == x_stride is
+// allowed (exact in place), no other overlap.
+template <typename T>
+int dct_dev(const pdsp_plan *plan, long long batch, const T *x, long long x_stride, int type, T g, T g0, T *y,
+            long long y_stride, hipStream_t s);
+// the 16-byte path's condition: both row pointers 16-byte aligned, both strides multiples of 16 bytes
+bool dct_fast_path(const void *x, long long x_stride, const void *y, long long y_stride, size_t elem);
 
 }  // namespace pdsp_host

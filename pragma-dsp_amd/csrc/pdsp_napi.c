@@ -615,6 +615,28 @@ static napi_value Istft(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* dct(type, norm, x, y): y receives the dct of one signal of x.length values (type 2 / 3, norm a pdsp_dct_norm).  The
+ * integers are read first and the two typed-array pointers last, one after the other, with no user JS between
+ * them.  A length the library refuses reaches it unchanged, so its message is what the caller sees. */
+static napi_value Dct(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return NULL;
+  int64_t type, norm;
+  double *x, *y;
+  size_t nx, ny;
+  if (!get_i64(env, argv[0], &type) || !get_i64(env, argv[1], &norm) || !f64_array(env, argv[2], &x, &nx) ||
+      !f64_array(env, argv[3], &y, &ny))
+    return NULL;
+  if (ny < nx) {
+    napi_throw_error(env, NULL, "pdsp_napi: dct output too small");
+    return NULL;
+  }
+  if (type < INT32_MIN || type > INT32_MAX) type = 0; /* refused by the library as "type must be 2 or 3" */
+  if (norm < INT32_MIN || norm > INT32_MAX) norm = -1;
+  if (pdsp_dct_host_f64(x, 1, (long long)nx, (int)type, (int)norm, y) != PDSP_OK) return throw_pdsp(env);
+  return NULL;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   const struct {
     const char *name;
@@ -627,6 +649,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"spectrumBatch", SpectrumBatch}, {"spectrumRows", SpectrumRows},
       {"nextPow2", NextPow2},     {"deviceCount", DeviceCount},
       {"firFilter", FirFilter},   {"stft", Stft},               {"istft", Istft},
+      {"dct", Dct},
   };
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
     napi_value f;

@@ -3,12 +3,14 @@ import * as coreNs from './core';
 import * as fourierNs from './fourier';
 import * as filtersNs from './filters';
 import * as stftNs from './stft';
+import * as dctNs from './dct';
 
 export { spectrum, spectrumBatch, spectrumStream, SpectrumOptions, SpectrumPeak, SpectrumResult } from './spectrum';
 export { ComplexArray } from './core';
 export { WindowType } from './fourier';
 export { FirMode, FirFilterOptions } from './filters';
 export { StftWindow, StftOptions, StftResult } from './stft';
+export { DctType, DctNorm, DctOptions } from './dct';
 
 export const core: {
   createComplexArray: typeof coreNs.createComplexArray;
@@ -32,4 +34,8 @@ export const filters: {
 export const stft: {
   stft: typeof stftNs.stft;
   istft: typeof stftNs.istft;
+};
+export const dct: {
+  dct: typeof dctNs.dct;
+  idct: typeof dctNs.idct;
 };

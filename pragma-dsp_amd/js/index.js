@@ -5,11 +5,13 @@
 //   require('.../js').fourier    -> pragma-dsp/xform/fourier
 //   require('.../js').filters    -> pragma-dsp/filters (ROADMAP.md, "Filters and utilities")
 //   require('.../js').stft       -> pragma-dsp/xform/stft (ROADMAP.md, "A) STFT")
+//   require('.../js').dct        -> pragma-dsp/xform/dct (ROADMAP.md, v0.3)
 const core = require('./core');
 const fourier = require('./fourier');
 const s = require('./spectrum');
 const filters = require('./filters');
 const stft = require('./stft');
+const dct = require('./dct');
 
 module.exports = {
   spectrum: s.spectrum,
@@ -41,5 +43,10 @@ Object.defineProperty(module.exports, 'filters', {
 // pragma-dsp/xform/stft: planned by the reference (ROADMAP.md, "A) STFT"), not enumerated for the same reason.
 Object.defineProperty(module.exports, 'stft', {
   value: { stft: stft.stft, istft: stft.istft },
+  enumerable: false,
+});
+// pragma-dsp/xform/dct: planned by the reference (ROADMAP.md, v0.3), not enumerated for the same reason.
+Object.defineProperty(module.exports, 'dct', {
+  value: { dct: dct.dct, idct: dct.idct },
   enumerable: false,
 });
