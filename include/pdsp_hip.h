@@ -272,7 +272,7 @@ PDSP_API int pdsp_spectrum_peaks_f32(const pdsp_plan *plan, long long batch,
 
 /* ---- the same device-pointer family in f64 ------------------------------ */
 /* Identical contracts with double rows, N <= 2^26 (PDSP_ERR_UNSUPPORTED_SIZE beyond).
- * ~1e-15 relative to max vs the f64 reference. */
+ * Per bin, 2.3e-16 * log2 N of the row's rms at most (measured against long-double references). */
 PDSP_API int pdsp_fft_forward_real_f64(const pdsp_plan *plan, long long batch,
                                        const double *re_in, double *re_out, double *im_out,
                                        pdsp_stream stream);

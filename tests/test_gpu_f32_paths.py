@@ -114,7 +114,8 @@ def _transform_path(kind, L, offs, aliased, sw):
             names.add("tilepass-3-scratch2")
         return names | _tile_names(_three(L), True, tp)
     if L > 18:
-        return {"bigfft"}
+        # bigfft_rows: N1 = 2^(L - 14) rows; at N = 2^28 N1 == N2 and the first row pass is launch_rows (N = 16384)
+        return {"bigfft", "bigfft-n1-rows", "fft_split4_kernel"} if L == 28 and sw["split16k"] else {"bigfft"}
     if L > 14:
         return {"fourstep-fused"}
     if 1 <= L <= 4 and sw["staged_small"] and a16:
@@ -151,7 +152,8 @@ def _spectrum_path(L, batch, offs, frame_len, stride, window, sides, outputs, sw
     plan_win = window[1] if window and window[0] == "plan" else None
     rect_plan = plan_win == "rect"
     if L > 14:
-        if (sw["twopass"] & 1) and used == n and stride % 4 == 0 and _a(16, f_off, w_off):
+        # the packed tile-pass tables (hp_np) exist for 2^15 ... 2^27 only
+        if L <= 27 and (sw["twopass"] & 1) and used == n and stride % 4 == 0 and _a(16, f_off, w_off):
             first = 3 if (window is None or rect_plan) else 4
             if plan_win in FUSED and sw["fused_window"]:
                 first = 5 if plan_win != "blackman" else 6
@@ -165,6 +167,8 @@ def _spectrum_path(L, batch, offs, frame_len, stride, window, sides, outputs, sw
                 names = {"tilepass_chain-packed"} | _tile_names(ls, False, sw["twopass"])
             return names | {f"packed-first{first}", "split_amp_rows_kernel"} | _peak_names(bins, outputs)
         names = {"bigfft_out<AMP>"} if L > 18 else {"fourstep_ab/c-mode1"}
+        if L == 28 and sw["split16k"]:
+            names |= {"bigfft-n1-rows", "fft_split4_kernel"}
         return names | _peak_names(bins, outputs)
     if L >= 6:
         fast = _a(8, f_off, w_off) and stride % 2 == 0 and used == n and sides == "one" and "ph" not in outputs
@@ -197,7 +201,7 @@ REQUIRED = {
     # transforms
     "fft_tiny_staged_kernel", "fft_stockham_kernel", "fft_staged_kernel", "fft_split2_kernel", "fft_split4_kernel",
     "fft_paired_kernel", "tilepass-2", "tilepass-3", "tilepass-3-perm", "tilepass-3-natural", "tilepass-3-scratch2",
-    "tile_pass_kernel", "tile_cols512_kernel", "tile_rows512_kernel", "fourstep-fused", "bigfft",
+    "tile_pass_kernel", "tile_cols512_kernel", "tile_rows512_kernel", "fourstep-fused", "bigfft", "bigfft-n1-rows",
     # spectra
     "fft_tiny_staged_kernel<AMP>", "small-complex-(x,0)", "spectrum_staged_kernel",
     *[f"spectrum_packed_kernel-{f}-m{m}-w{w}" for f in ("FAST", "general") for m in range(5, 14) for w in (0, 1)],
@@ -215,8 +219,8 @@ REQUIRED = {
 # ---- buffers ----------------------------------------------------------------------------------------------------
 
 class Buf:
-    """`rows` rows of `length` floats, `stride` apart, starting `off` floats past a 4 KiB aligned base that follows
-    GUARD floats of `fill`; GUARD more after the last row.  Everything outside the rows holds `fill`."""
+    """`rows` rows of `length` elements, `stride` apart, starting `off` elements past a 4 KiB aligned base that follows
+    GUARD elements of `fill`; GUARD more after the last row.  Everything outside the rows holds `fill`."""
 
     def __init__(self, rows, length, off=0, stride=None, fill=float("nan"), dtype=None):
         import torch
@@ -227,7 +231,7 @@ class Buf:
         span = max(rows - 1, 0) * self.stride + length
         self.flat = torch.full((self.start + span + GUARD,), fill, dtype=dtype, device="cuda:0")
         self.view = torch.as_strided(self.flat, (rows, length), (self.stride, 1), self.start)
-        self.ptr = self.flat.data_ptr() + 4 * self.start
+        self.ptr = self.flat.data_ptr() + self.flat.element_size() * self.start
         self.fill = fill
 
     def set(self, a):
@@ -267,7 +271,7 @@ class Switches:
     """Development switches for one case, restored in finally (the previous value is what each setter returns)."""
 
     SETTERS = {"split16k": "pdsp_set_split16k", "twopass": "pdsp_set_twopass", "staged_small": "pdsp_set_staged_small",
-               "fused_window": "pdsp_set_fused_window"}
+               "fused_window": "pdsp_set_fused_window", "real_packed": "pdsp_set_real_packed"}
 
     def __init__(self, sw):
         self.sw = sw or {}
@@ -510,6 +514,8 @@ TRANSFORM_CASES = [
     ("fourstep-unaligned", range(15, 19), 2, T, (1, 2, 0, 3), "disjoint", None, {"fourstep-fused"}),
     ("bigfft-unaligned", range(19, 22), 1, T, (2, 0, 1, 0), "disjoint", None, {"bigfft"}),
     ("bigfft-inplace", range(19, 20), 2, ("complex", "inverse"), (3, 1, 0, 0), "inplace", None, {"bigfft"}),
+    # N = 1 << 28, the largest f32 size: N1 = N2 = 16384, so bigfft_rows' first row pass is launch_rows
+    ("bigfft-2p28", range(28, 29), 1, T, (0, 0, 0, 0), "disjoint", None, {"bigfft-n1-rows"}),
 ]
 
 def _tf_kind(kind):
@@ -761,6 +767,8 @@ SPEC_CASES = [
     ("fourstep-spec-twopass0", range(15, 17), 2, "full", "len", 0, (None,), 0, ("one",), (A,), {"twopass": 0}),
     ("bigfft-spec", range(19, 22), 1, "part", "len", 0, (("plan", "hann"),), 0, ("one",), (P, R), None),
     ("bigfft-spec-stride", range(19, 20), 2, "full", "gap1", 0, (None,), 0, ("one",), (A, I), None),
+    # N = 1 << 28: no packed tile-pass tables, so whole aligned frames take bigfft AMP too (launch_rows N1 pass)
+    ("bigfft-spec-2p28", range(28, 29), 1, "full", "len", 0, (("plan", "hann"),), 0, ("one",), (A, I), None),
     ("memset", range(0, 15, 7), 3, "zero", "gap1", 0, (None,), 0, ("one", "two"), (P, I, R), None),
 ]
 
@@ -786,7 +794,8 @@ SPEC_WANT = {
     "chain-3pass-natural": ("tilepass_chain-packed",), "chain-512": ("tilepass_chain-packed",),
     "fourstep-spec-part": ("fourstep_ab/c-mode1",), "fourstep-spec-unaligned": ("fourstep_ab/c-mode1",),
     "fourstep-spec-stride": ("fourstep_ab/c-mode1",), "fourstep-spec-twopass0": ("fourstep_ab/c-mode1",),
-    "bigfft-spec": ("bigfft_out<AMP>",), "bigfft-spec-stride": ("bigfft_out<AMP>",), "memset": ("memset",),
+    "bigfft-spec": ("bigfft_out<AMP>",), "bigfft-spec-stride": ("bigfft_out<AMP>",),
+    "bigfft-spec-2p28": ("bigfft-n1-rows",), "memset": ("memset",),
 }
 
 
