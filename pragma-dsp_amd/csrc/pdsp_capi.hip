@@ -1462,13 +1462,22 @@ int spectrum_frames_host(const FrameSource &in, long long batch, double sample_r
 
 namespace pdsp_host {
 
-// Filters run on the packed-real tables (N = 64 ... 16384 in both precisions) with at most N/2 taps.
+// The packed-real kernels (FIR filtering, the short-time pair, the DCT) run on the N/2-point tables, N = 64 ... 16384
+// in both precisions; the DCT also on W_4N^k.  `what` names the feature in the error text.
+template <typename T>
+int check_packed_plan(const pdsp_plan *plan, const char *what, bool need_tw4n) {
+  if (!plan) return fail(PDSP_ERR_BAD_ARG, "plan is null");
+  const Tables<T> &t = tables<T>(plan);
+  if (plan->log2n < 6 || plan->log2n > pdsp::kMaxLog2N_f32 || !t.tw_half || !t.twr || (need_tw4n && !t.tw4n))
+    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "%s needs a plan of 64 <= N <= 16384, got %lld", what, plan->n);
+  return PDSP_OK;
+}
+
+// Filters have at most N/2 taps (the tap count is checked ahead of the plan's size, behind its null check).
 template <typename T>
 int check_fir_plan(const pdsp_plan *plan, long long ntaps) {
-  if (!plan) return fail(PDSP_ERR_BAD_ARG, "plan is null");
-  if (ntaps < 1) return fail(PDSP_ERR_BAD_ARG, "filter must have at least one tap, got %lld", ntaps);
-  if (plan->log2n < 6 || plan->log2n > pdsp::kMaxLog2N_f32 || !tables<T>(plan).tw_half || !tables<T>(plan).twr)
-    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "FIR filtering needs a plan of 64 <= N <= 16384, got %lld", plan->n);
+  if (plan && ntaps < 1) return fail(PDSP_ERR_BAD_ARG, "filter must have at least one tap, got %lld", ntaps);
+  if (int rc = check_packed_plan<T>(plan, "FIR filtering", false)) return rc;
   if (ntaps > plan->n / 2)
     return fail(PDSP_ERR_UNSUPPORTED_SIZE, "filter of %lld taps exceeds N/2 = %lld of the plan (no partitioned convolution)",
                 ntaps, plan->n / 2);
@@ -1509,11 +1518,9 @@ int fir_filter_t(const pdsp_plan *plan, long long batch, const T *x, long long l
   if (!y || (len > 0 && (!x || !h_re || !h_im))) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   // blocks of a row read input that other blocks overwrite when y shares bytes with x: the result would depend on
   // the order in which workgroups run.  Byte ranges of the whole strided extent, as planes_overlap()
-  if (len > 0) {
-    const char *xb = (const char *)x, *yb = (const char *)y;
-    const size_t xn = (size_t)((batch - 1) * x_stride + len) * sizeof(T), yn = (size_t)((batch - 1) * y_stride + y_len) * sizeof(T);
-    if (xb < yb + yn && yb < xb + xn) return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
-  }
+  if (len > 0 && host_ranges_overlap(x, (size_t)((batch - 1) * x_stride + len) * sizeof(T), y,
+                                     (size_t)((batch - 1) * y_stride + y_len) * sizeof(T)))
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
   // an even filter runs with one zero tap more (same H): P odd makes hop = N - P + 1 even, the aligned fast path
   const int p = (int)(ntaps % 2 == 1 ? ntaps : ntaps + 1);
   const long long hop = plan->n - (p - 1);
@@ -1621,24 +1628,10 @@ int pdsp_fir_filter_host_f64(const double *x, long long batch, long long len, co
 
 namespace pdsp_host {
 
-// The short-time pair runs on the packed-real tables (N = 64 ... 16384 in both precisions), as FIR filtering.
-template <typename T>
-int check_stft_plan(const pdsp_plan *plan) {
-  if (!plan) return fail(PDSP_ERR_BAD_ARG, "plan is null");
-  if (plan->log2n < 6 || plan->log2n > pdsp::kMaxLog2N_f32 || !tables<T>(plan).tw_half || !tables<T>(plan).twr)
-    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "STFT needs a plan of 64 <= N <= 16384, got %lld", plan->n);
-  return PDSP_OK;
-}
-
-inline bool bytes_meet(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-  const char *ca = (const char *)a, *cb = (const char *)b;
-  return b && a && ca < cb + b_bytes && cb < ca + a_bytes;
-}
-
 template <typename T>
 int stft_complex_t(const pdsp_plan *plan, long long batch, const T *frames, long long frame_len, long long frame_stride,
                    const T *window, T *re_out, T *im_out, hipStream_t s) {
-  if (int rc = check_stft_plan<T>(plan)) return rc;
+  if (int rc = check_packed_plan<T>(plan, "STFT", false)) return rc;
   if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "frames must be >= 1, got %lld", batch);
   if (frame_len < 1) return fail(PDSP_ERR_BAD_ARG, "frame_len must be >= 1, got %lld", frame_len);
   if (frame_stride < 1) return fail(PDSP_ERR_BAD_ARG, "frame_stride (hop) must be >= 1, got %lld", frame_stride);
@@ -1650,8 +1643,9 @@ int stft_complex_t(const pdsp_plan *plan, long long batch, const T *frames, long
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
   if (!frames || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   const size_t ib = (size_t)in_count * sizeof(T), ob = (size_t)out_count * sizeof(T), wb = (size_t)n * sizeof(T);
-  if (bytes_meet(re_out, ob, frames, ib) || bytes_meet(im_out, ob, frames, ib) || bytes_meet(re_out, ob, im_out, ob) ||
-      bytes_meet(re_out, ob, window, wb) || bytes_meet(im_out, ob, window, wb))
+  if (host_ranges_overlap(re_out, ob, frames, ib) || host_ranges_overlap(im_out, ob, frames, ib) ||
+      host_ranges_overlap(re_out, ob, im_out, ob) || host_ranges_overlap(re_out, ob, window, wb) ||
+      host_ranges_overlap(im_out, ob, window, wb))
     return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
   DeviceGuard g(plan->device);
   PDSP_HIP_TRY(g.err);
@@ -1661,7 +1655,7 @@ int stft_complex_t(const pdsp_plan *plan, long long batch, const T *frames, long
 template <typename T>
 int istft_t(const pdsp_plan *plan, long long frames, const T *re_in, const T *im_in, long long hop, const T *window, T *out,
             hipStream_t s) {
-  if (int rc = check_stft_plan<T>(plan)) return rc;
+  if (int rc = check_packed_plan<T>(plan, "STFT", false)) return rc;
   if (frames < 1) return fail(PDSP_ERR_BAD_ARG, "frames must be >= 1, got %lld", frames);
   if (hop < 1) return fail(PDSP_ERR_BAD_ARG, "hop must be >= 1, got %lld", hop);
   if (frames > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", frames);
@@ -1672,7 +1666,8 @@ int istft_t(const pdsp_plan *plan, long long frames, const T *re_in, const T *im
     return fail(PDSP_ERR_BAD_ARG, "frames %lld x hop %lld overflows", frames, hop);
   if (!re_in || !im_in || !out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   const size_t ib = (size_t)in_count * sizeof(T), ob = (size_t)total * sizeof(T), wb = (size_t)n * sizeof(T);
-  if (bytes_meet(out, ob, re_in, ib) || bytes_meet(out, ob, im_in, ib) || bytes_meet(out, ob, window, wb))
+  if (host_ranges_overlap(out, ob, re_in, ib) || host_ranges_overlap(out, ob, im_in, ib) ||
+      host_ranges_overlap(out, ob, window, wb))
     return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
   DeviceGuard g(plan->device);
   PDSP_HIP_TRY(g.err);
@@ -1796,16 +1791,6 @@ int pdsp_istft_host_f64(const double *re, const double *im, long long frames, lo
 
 namespace pdsp_host {
 
-// The DCT runs on the packed-real tables plus W_4N^k (N = 64 ... 16384 in both precisions), as the short-time pair.
-template <typename T>
-int check_dct_plan(const pdsp_plan *plan) {
-  if (!plan) return fail(PDSP_ERR_BAD_ARG, "plan is null");
-  if (plan->log2n < 6 || plan->log2n > pdsp::kMaxLog2N_f32 || !tables<T>(plan).tw_half || !tables<T>(plan).twr ||
-      !tables<T>(plan).tw4n)
-    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "DCT needs a plan of 64 <= N <= 16384, got %lld", plan->n);
-  return PDSP_OK;
-}
-
 int check_dct_type_norm(int type, int norm) {
   if (type != 2 && type != 3) return fail(PDSP_ERR_BAD_ARG, "DCT type must be 2 or 3, got %d", type);
   if (norm < PDSP_DCT_BACKWARD || norm > PDSP_DCT_FORWARD)
@@ -1830,7 +1815,7 @@ void dct_scales(long long n, int type, int norm, double *g, double *g0) {
 template <typename T>
 int dct_t(const pdsp_plan *plan, long long batch, const T *x, long long x_stride, int type, int norm, T *y,
           long long y_stride, hipStream_t s) {
-  if (int rc = check_dct_plan<T>(plan)) return rc;
+  if (int rc = check_packed_plan<T>(plan, "DCT", true)) return rc;
   const long long n = plan->n;
   if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
   if (x_stride < n || y_stride < n)
@@ -1845,7 +1830,7 @@ int dct_t(const pdsp_plan *plan, long long batch, const T *x, long long x_stride
   // exact in place is safe (each row is loaded in full by its own workgroup before that workgroup's first barrier);
   // any other overlap would let one row's stores reach another row's loads
   const bool in_place = (const void *)x == (const void *)y && x_stride == y_stride;
-  if (!in_place && bytes_meet(y, (size_t)yc * sizeof(T), x, (size_t)xc * sizeof(T)))
+  if (!in_place && host_ranges_overlap(y, (size_t)yc * sizeof(T), x, (size_t)xc * sizeof(T)))
     return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only y == x with y_stride == x_stride may share bytes)");
   double g = 1.0, g0 = 1.0;
   dct_scales(n, type, norm, &g, &g0);

@@ -1,17 +1,17 @@
 // pdsp_dct_kernel.h -- DCT-II and DCT-III of rows of N = 2M = 64 ... 16384 real values (scipy dct / idct,
 // types 2 and 3), one row per TP = M/16 threads, one launch per call, N values in and N values out per row.
 //
-// DCT-II (dct2_kernel), Makhoul's algorithm on the packed-real forward of stft_complex_kernel:
+// DCT-II (dct2_kernel), Makhoul's algorithm on the packed-real row of pdsp_packed.h:
 //   1. v[n] = x[2n], v[N-1-n] = x[2n+1] (n < M), packed z[m] = v[2m] + i v[2m+1]: for m < M/2
 //      z[m] = x[4m] + i x[4m+2] and z[M-1-m] = x[4m+3] + i x[4m+1] -- one quad x[4m ... 4m+3] feeds slot q of thread
 //      tid (m = tid + TP q) and slot E-1-q of thread TP-1-tid;
-//   2. V = rfft(v), bins k and M-k from the Hermitian split of Z = FFT_M(z) (stft_complex_kernel, steps 1-2);
+//   2. V = rfft(v), bins k and M-k from the forward split of Z = FFT_M(z);
 //   3. c_k = W_4N^k V[k]: y[k] = 2 Re c_k, y[N-k] = -2 Im c_k.  The thread that owns the pair (k, M-k) writes y[k],
 //      y[N-k], y[M-k], y[M+k]; k = 0 gives y[0] and y[M], k = M/2 (its own partner) y[M/2] and y[3M/2].
-// DCT-III (dct3_kernel), the mirror (istft_frame_kernel's inverse split and pass set):
+// DCT-III (dct3_kernel), the mirror:
 //   4. V[k] = conj(W_4N^k) (y[k] - i y[N-k]), y[N] := 0, k = 0 ... M (V[0], V[M] real: their imaginary parts are
 //      dropped), the inverse split of the pair (k, M-k) into the row's LDS;
-//   5. one forward pass set on conj(Z') gives conj(v[2m] + i v[2m+1]), v = N irfft(V) = 2N idct-II(y);
+//   5. the second transform gives conj(v[2m] + i v[2m+1]), v = N irfft(V) = 2N idct-II(y);
 //   6. x[2n] = v[n], x[2n+1] = v[N-1-n]: slot q of m < M/2 goes to x[4m], x[4m+2], of m >= M/2 to x[4m'+3], x[4m'+1],
 //      m' = M-1-m.
 // Norms: every output of the DCT-II is scaled by g and y[0] by g0 instead; every input of the DCT-III by g and y[0]
@@ -23,7 +23,7 @@
 // workgroup's first barrier, and stored only after it.
 #pragma once
 
-#include "pdsp_fft_kernel.h"
+#include "pdsp_packed.h"
 
 namespace pdsp {
 
@@ -58,30 +58,19 @@ __global__ void __launch_bounds__(kPackedWG<LOG2M>)
 dct2_kernel(const T *x, const long long x_stride, T *y, const long long y_stride,
             const typename vec2<T>::type *__restrict__ tw, const typename vec2<T>::type *__restrict__ twr,
             const typename vec2<T>::type *__restrict__ tw4, const T g, const T g0, const long long batch) {
-  constexpr int LOG2E = packed_log2e(LOG2M);
-  using TR = FftTraits<LOG2M, LOG2E>;
-  constexpr int E = TR::E, TP = TR::TP, M = TR::N, N = 2 * M;
-  static_assert(LOG2M >= 5 && LOG2E == 4, "packed path: TP >= 2, sixteen points per thread (W_N^(TP q) = W_32^q)");
+  using PR = PackedRow<T, LOG2M>;
+  constexpr int E = PR::E, TP = PR::TP, M = PR::M, N = 2 * M;
   static_assert(TP * E / 2 == M / 2, "slots q < E/2 hold m < M/2");
 
-  __shared__ cx<T> lds[TR::LDS_ELEMS];
-
-  const int tid = (int)(threadIdx.x % TP);
-  const int rloc = (int)(threadIdx.x / TP);
-  const long long row_raw = (long long)blockIdx.x * TR::ROWS + rloc;
-  const bool live = row_raw < batch;
-  // dead rows of the last workgroup recompute the last live row and skip the stores: every thread reaches every
-  // barrier (batch < 2^31 is checked on the host)
-  const long long row = uniform_row<TP>(live ? row_raw : batch - 1);
-  cx<T> *const lrow = lds + rloc * TR::LROW;
+  __shared__ cx<T> lds[PR::TR::LDS_ELEMS];
+  const PR pr(lds, batch);
+  const int tid = pr.tid;
+  cx<T> *const lrow = pr.lrow;
   T *const lval = reinterpret_cast<T *>(lrow);  // N plain values (LROW >= M complex)
-  const T *const xrow = x + (size_t)row * (size_t)x_stride;
+  const T *const xrow = x + (size_t)pr.row * (size_t)x_stride;
 
-  constexpr bool kRegTw = TP >= 16;
-  std::conditional_t<kRegTw, RegTwiddles<T, LOG2M, LOG2E>, TableTwiddles<T, LOG2M, LOG2E>> twf;
-  if constexpr (kRegTw) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
-  else twf.tw = reinterpret_cast<const cx<T> *>(tw);
-  const cx<T> twk0 = reinterpret_cast<const cx<T> *>(twr)[(unsigned)tid];  // W_N^tid; W_N^(tid + TP q) = twk0 W_32^q
+  PackedTwiddles<T, LOG2M> twd;
+  twd.load(tw, twr, tid);
   load_order_fence();
 
   cx<T> z[E];
@@ -94,7 +83,7 @@ dct2_kernel(const T *x, const long long x_stride, T *y, const long long y_stride
       lrow[lds_pad(M - 1 - m)] = cx<T>{v[q][3], v[q][1]};
     });
     __syncthreads();
-    fft_pass_readback<T, LOG2M, LOG2E>(z, lrow, tid);
+    fft_pass_readback<T, LOG2M, PR::LOG2E>(z, lrow, tid);
     __syncthreads();  // the first pass writes LDS again
   } else {
     static_for<E>([&](auto qc) {
@@ -109,54 +98,44 @@ dct2_kernel(const T *x, const long long x_stride, T *y, const long long y_stride
     });
   }
 
-  fft_passes<T, LOG2M, true, LOG2E>(z, lrow, twf, tid);  // Z in LDS, natural order
+  fft_passes<T, LOG2M, true, PR::LOG2E>(z, lrow, twd.twf, tid);  // Z in LDS, natural order
   __syncthreads();
   if constexpr (!FAST)
-    if (!live) return;  // no barrier below
+    if (!pr.live) return;  // no barrier below
 
-  T *const yrow = y + (size_t)row * (size_t)y_stride;
+  T *const yrow = y + (size_t)pr.row * (size_t)y_stride;
   const cx<T> *const w4 = reinterpret_cast<const cx<T> *>(tw4);
   T o[E / 2 + 1][4];  // y[k], y[N-k], y[M-k], y[M+k] of pair q (FAST: held across the barrier below)
-  // pairs k = tid + TP q, q < E/2 (k < M/2); k = M/2 is one more pair for tid == 0 (it pairs with itself)
-  static_for<E / 2 + 1>([&](auto qc) {
-    constexpr int q = qc;
-    if (q < E / 2 || tid == 0) {
-      const int k = tid + TP * q, k2 = (M - k) & (M - 1);  // k = 0: Z[M] == Z[0]
-      const cx<T> zk = lrow[lds_pad(k)], zp = lrow[lds_pad(k2)];
-      const cx<T> w = mul_w32<T, q>(twk0);  // W_N^k
-      const cx<T> sm = zk + conj(zp), pm = cmul(zk - conj(zp), w);
-      const cx<T> ca = cmul(add_mul_neg_i(sm, pm), w4[k]);        // 2 V[k] W_4N^k
-      const cx<T> cb = cmul(conj(add_mul_pos_i(sm, pm)), w4[M - k]);  // 2 V[M-k] W_4N^(M-k)
-      o[q][0] = ca.x * (k == 0 ? g0 : g);
-      o[q][1] = -ca.y * g;
-      o[q][2] = cb.x * g;
-      o[q][3] = -cb.y * g;
-      if constexpr (!FAST) {
-        yrow[k] = o[q][0];
-        if (k != 0) yrow[N - k] = o[q][1];
-        if (k != M / 2) {
-          yrow[M - k] = o[q][2];
-          if (k != 0) yrow[M + k] = o[q][3];
-        }
+  pr.for_each_pair([&](auto q, const int k) {
+    const auto sp = pr.forward_split(k, (M - k) & (M - 1));
+    const cx<T> w = twd.wk(q);  // W_N^k
+    const cx<T> ca = cmul(sp.x(w), w4[k]);       // 2 V[k] W_4N^k
+    const cx<T> cb = cmul(sp.xm(w), w4[M - k]);  // 2 V[M-k] W_4N^(M-k)
+    o[q][0] = ca.x * (k == 0 ? g0 : g);
+    o[q][1] = -ca.y * g;
+    o[q][2] = cb.x * g;
+    o[q][3] = -cb.y * g;
+    if constexpr (!FAST) {
+      yrow[k] = o[q][0];
+      if (k != 0) yrow[N - k] = o[q][1];
+      if (k != M / 2) {
+        yrow[M - k] = o[q][2];
+        if (k != 0) yrow[M + k] = o[q][3];
       }
     }
   });
   if constexpr (FAST) {
     __syncthreads();  // every Z read: the plain values take the row's LDS
-    static_for<E / 2 + 1>([&](auto qc) {
-      constexpr int q = qc;
-      if (q < E / 2 || tid == 0) {
-        const int k = tid + TP * q;
-        lval[k] = o[q][0];
-        if (k != 0) lval[N - k] = o[q][1];
-        if (k != M / 2) {
-          lval[M - k] = o[q][2];
-          if (k != 0) lval[M + k] = o[q][3];
-        }
+    pr.for_each_pair([&](auto q, const int k) {
+      lval[k] = o[q][0];
+      if (k != 0) lval[N - k] = o[q][1];
+      if (k != M / 2) {
+        lval[M - k] = o[q][2];
+        if (k != 0) lval[M + k] = o[q][3];
       }
     });
     __syncthreads();
-    if (!live) return;
+    if (!pr.live) return;
     static_for<E / 2>([&](auto q) {
       const int c = 4 * (tid + TP * q);
       T v[4] = {lval[c], lval[c + 1], lval[c + 2], lval[c + 3]};
@@ -171,24 +150,19 @@ __global__ void __launch_bounds__(kPackedWG<LOG2M>)
 dct3_kernel(const T *x, const long long x_stride, T *y, const long long y_stride,
             const typename vec2<T>::type *__restrict__ tw, const typename vec2<T>::type *__restrict__ twr,
             const typename vec2<T>::type *__restrict__ tw4, const T g, const T g0, const long long batch) {
-  constexpr int LOG2E = packed_log2e(LOG2M);
-  using TR = FftTraits<LOG2M, LOG2E>;
-  constexpr int E = TR::E, TP = TR::TP, M = TR::N, N = 2 * M;
-  static_assert(LOG2M >= 5 && LOG2E == 4, "packed path: TP >= 2, sixteen points per thread (W_N^(TP q) = W_32^q)");
+  using PR = PackedRow<T, LOG2M>;
+  constexpr int E = PR::E, TP = PR::TP, M = PR::M, N = 2 * M;
   static_assert(TP * E / 2 == M / 2, "slots q < E/2 hold m < M/2");
 
-  __shared__ cx<T> lds[TR::LDS_ELEMS];
+  __shared__ cx<T> lds[PR::TR::LDS_ELEMS];
+  const PR pr(lds, batch);
+  const int tid = pr.tid;
+  cx<T> *const lrow = pr.lrow;
+  T *const lval = reinterpret_cast<T *>(lrow);  // N plain values (LROW >= M complex)
+  const T *const xrow = x + (size_t)pr.row * (size_t)x_stride;
 
-  const int tid = (int)(threadIdx.x % TP);
-  const int rloc = (int)(threadIdx.x / TP);
-  const long long row_raw = (long long)blockIdx.x * TR::ROWS + rloc;
-  const bool live = row_raw < batch;
-  const long long row = uniform_row<TP>(live ? row_raw : batch - 1);
-  cx<T> *const lrow = lds + rloc * TR::LROW;
-  T *const lval = reinterpret_cast<T *>(lrow);
-  const T *const xrow = x + (size_t)row * (size_t)x_stride;
-
-  const cx<T> twk0 = reinterpret_cast<const cx<T> *>(twr)[(unsigned)tid];  // W_N^tid
+  PackedTwiddles<T, LOG2M> twd;
+  twd.load_split(twr, tid);
   const cx<T> *const w4 = reinterpret_cast<const cx<T> *>(tw4);
   // inputs of pair q: x[k], x[N-k] (x[0] read for k = 0, then dropped), x[M-k], x[M+k]
   T a[E / 2 + 1][4];
@@ -200,50 +174,30 @@ dct3_kernel(const T *x, const long long x_stride, T *y, const long long y_stride
       lval[c] = v[q][0], lval[c + 1] = v[q][1], lval[c + 2] = v[q][2], lval[c + 3] = v[q][3];
     });
     __syncthreads();
-    static_for<E / 2 + 1>([&](auto qc) {
-      constexpr int q = qc;
-      if (q < E / 2 || tid == 0) {
-        const int k = tid + TP * q;
-        a[q][0] = lval[k], a[q][1] = lval[(N - k) & (N - 1)], a[q][2] = lval[M - k], a[q][3] = lval[M + k];
-      }
+    pr.for_each_pair([&](auto q, const int k) {
+      a[q][0] = lval[k], a[q][1] = lval[(N - k) & (N - 1)], a[q][2] = lval[M - k], a[q][3] = lval[M + k];
     });
     __syncthreads();  // every plain value read: the split takes the row's LDS
   } else {
-    static_for<E / 2 + 1>([&](auto qc) {
-      constexpr int q = qc;
-      if (q < E / 2 || tid == 0) {
-        const int k = tid + TP * q;
-        a[q][0] = ld_stream(xrow + (unsigned)k), a[q][1] = ld_stream(xrow + (unsigned)((N - k) & (N - 1)));
-        a[q][2] = ld_stream(xrow + (unsigned)(M - k)), a[q][3] = ld_stream(xrow + (unsigned)(M + k));
-      }
+    pr.for_each_pair([&](auto q, const int k) {
+      a[q][0] = ld_stream(xrow + (unsigned)k), a[q][1] = ld_stream(xrow + (unsigned)((N - k) & (N - 1)));
+      a[q][2] = ld_stream(xrow + (unsigned)(M - k)), a[q][3] = ld_stream(xrow + (unsigned)(M + k));
     });
   }
 
-  // V[k], V[M-k] and the inverse split of the pair (k, M-k) into the row's LDS (every slot has one owner)
-  static_for<E / 2 + 1>([&](auto qc) {
-    constexpr int q = qc;
-    if (q < E / 2 || tid == 0) {
-      const int k = tid + TP * q, k2 = M - k;  // k = 0 pairs with the Nyquist bin M
-      cx<T> va = cmul(cx<T>{a[q][0] * (k == 0 ? g0 : g), k == 0 ? T(0) : -a[q][1] * g}, conj(w4[k]));
-      cx<T> vb = cmul(cx<T>{a[q][2] * g, -a[q][3] * g}, conj(w4[k2]));
-      if (k == 0) va.y = vb.y = T(0);  // V[0] and V[M] are real
-      const cx<T> w = mul_w32<T, q>(twk0);  // W_N^k
-      const cx<T> s = va + conj(vb), c = cmul(va - conj(vb), conj(w));
-      lrow[lds_pad(k)] = conj(add_mul_pos_i(s, c));                    // conj Z'[k]
-      if (k != 0 && k2 != k) lrow[lds_pad(k2)] = add_mul_neg_i(s, c);  // conj Z'[M-k]
-    }
+  // V[k], V[M-k] and their inverse split
+  pr.for_each_pair([&](auto q, const int k) {
+    const int k2 = M - k;  // k = 0 pairs with the Nyquist bin M
+    cx<T> va = cmul(cx<T>{a[q][0] * (k == 0 ? g0 : g), k == 0 ? T(0) : -a[q][1] * g}, conj(w4[k]));
+    cx<T> vb = cmul(cx<T>{a[q][2] * g, -a[q][3] * g}, conj(w4[k2]));
+    if (k == 0) va.y = vb.y = T(0);  // V[0] and V[M] are real
+    pr.inverse_split(k, k2, va, vb, twd.wk(q));
   });
-  constexpr bool kRegTw = TP >= 16;
-  std::conditional_t<kRegTw, RegTwiddles<T, LOG2M, LOG2E>, TableTwiddles<T, LOG2M, LOG2E>> twf;
-  if constexpr (kRegTw) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
-  else twf.tw = reinterpret_cast<const cx<T> *>(tw);
+  twd.load_passes(tw, tid);
   cx<T> z[E];
-  __syncthreads();
-  fft_pass_readback<T, LOG2M, LOG2E>(z, lrow, tid);
-  __syncthreads();  // the first pass writes LDS again
-  fft_passes<T, LOG2M, false, LOG2E>(z, lrow, twf, tid);  // conj(v[2m] + i v[2m+1]) in slot q, m = tid + TP q
+  pr.second_transform(z, twd.twf);  // conj(v[2m] + i v[2m+1]) in slot q, m = tid + TP q
 
-  T *const yrow = y + (size_t)row * (size_t)y_stride;
+  T *const yrow = y + (size_t)pr.row * (size_t)y_stride;
   if constexpr (FAST) {
     __syncthreads();  // the last pass's read-back: the plain values take the row's LDS
     static_for<E>([&](auto qc) {
@@ -257,14 +211,14 @@ dct3_kernel(const T *x, const long long x_stride, T *y, const long long y_stride
       }
     });
     __syncthreads();
-    if (!live) return;
+    if (!pr.live) return;
     static_for<E / 2>([&](auto q) {
       const int c = 4 * (tid + TP * q);
       T v[4] = {lval[c], lval[c + 1], lval[c + 2], lval[c + 3]};
       st_quad(v, yrow + c);
     });
   } else {
-    if (!live) return;
+    if (!pr.live) return;
     static_for<E>([&](auto qc) {
       constexpr int q = qc;
       const int m = tid + TP * q;

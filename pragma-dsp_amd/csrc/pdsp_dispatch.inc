@@ -8,21 +8,6 @@
 
 namespace pdsp_host {
 
-template <int V>
-using int_c = std::integral_constant<int, V>;
-
-// A runtime int as a template argument: returns f(int_c<v>{}) for Lo <= v <= Hi and `outside` otherwise.  Only
-// the instances Lo ... Hi are compiled, so the range is the set of kernels built.
-template <int Lo, int Hi, class R, class F>
-R with_int(int v, R outside, const F &f) {
-  if constexpr (Lo <= Hi) {
-    if (v == Lo) return f(int_c<Lo>{});
-    return with_int<Lo + 1, Hi>(v, outside, f);
-  } else {
-    return outside;
-  }
-}
-
 // Are all the pointers multiples of `bytes` (a power of two)?  Null pointers are.
 template <class... P>
 bool aligned(size_t bytes, const P *...p) {

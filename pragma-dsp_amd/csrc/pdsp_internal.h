@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 #include "../../include/pdsp_hip.h"
 #include "../../include/pdsp_hip_dev.h"
@@ -223,6 +224,29 @@ inline int grid_for(long long total) {
   if (b > 2048) b = 2048;  // grid-stride the rest (256 CUs x 8)
   if (b < 1) b = 1;
   return (int)b;
+}
+
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// A runtime int as a template argument: returns f(int_c<v>{}) for Lo <= v <= Hi and `outside` otherwise.  Only
+// the instances Lo ... Hi are compiled, so the range is the set of kernels built.
+template <int Lo, int Hi, class R, class F>
+R with_int(int v, R outside, const F &f) {
+  if constexpr (Lo <= Hi) {
+    if (v == Lo) return f(int_c<Lo>{});
+    return with_int<Lo + 1, Hi>(v, outside, f);
+  } else {
+    return outside;
+  }
+}
+
+// Workgroups of a packed-real launch (pdsp_packed.h: PackedRow<T, LOG2M>::TR::ROWS rows each, kPackedWG<LOG2M>
+// threads) for `rows` rows; the packed sizes are 5 <= log2m <= 13 (N = 64 ... 16384)
+template <int LOG2M>
+dim3 packed_grid(long long rows) {
+  constexpr int R = pdsp::FftTraits<LOG2M, pdsp::packed_log2e(LOG2M)>::ROWS;
+  return dim3((unsigned)((rows + R - 1) / R));
 }
 
 // A launch of `blocks` workgroups for `batch` rows must fit grid.x (2^31 - 1)

@@ -5,17 +5,6 @@
 
 namespace pdsp_host {
 
-// f(integral_constant<log2m>) for the packed sizes 5 <= log2m <= 13 (N = 64 ... 16384)
-template <int Lo = 5, class F>
-static hipError_t with_int_dct(int log2m, const F &f) {
-  if constexpr (Lo <= 13) {
-    if (log2m == Lo) return f(std::integral_constant<int, Lo>{});
-    return with_int_dct<Lo + 1>(log2m, f);
-  } else {
-    return hipErrorInvalidValue;
-  }
-}
-
 bool dct_fast_path(const void *x, long long x_stride, const void *y, long long y_stride, size_t elem) {
   return ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && ((size_t)x_stride * elem) % 16 == 0 &&
          ((size_t)y_stride * elem) % 16 == 0;
@@ -26,17 +15,16 @@ int dct_dev(const pdsp_plan *plan, long long batch, const T *x, long long x_stri
             long long y_stride, hipStream_t s) {
   const Tables<T> &t = tables<T>(plan);
   const bool fast = dct_fast_path(x, x_stride, y, y_stride, sizeof(T));
-  const hipError_t e = with_int_dct(plan->log2n - 1, [&](auto L) {
+  const hipError_t e = with_int<5, 13>(plan->log2n - 1, hipErrorInvalidValue, [&](auto L) {
     constexpr int LOG2M = decltype(L)::value;
-    using TR = pdsp::FftTraits<LOG2M, pdsp::packed_log2e(LOG2M)>;
-    const long long ngroups = (batch + TR::ROWS - 1) / TR::ROWS;
+    const dim3 grid = packed_grid<LOG2M>(batch), wg(pdsp::kPackedWG<LOG2M>);
     auto go = [&](auto fast_c) {
       if (type == 2)
-        hipLaunchKernelGGL((pdsp::dct2_kernel<T, LOG2M, fast_c>), dim3((unsigned)ngroups), dim3(TR::WG), 0, s, x,
-                           x_stride, y, y_stride, t.tw_half, t.twr, t.tw4n, g, g0, batch);
+        hipLaunchKernelGGL((pdsp::dct2_kernel<T, LOG2M, fast_c>), grid, wg, 0, s, x, x_stride, y, y_stride, t.tw_half,
+                           t.twr, t.tw4n, g, g0, batch);
       else
-        hipLaunchKernelGGL((pdsp::dct3_kernel<T, LOG2M, fast_c>), dim3((unsigned)ngroups), dim3(TR::WG), 0, s, x,
-                           x_stride, y, y_stride, t.tw_half, t.twr, t.tw4n, g, g0, batch);
+        hipLaunchKernelGGL((pdsp::dct3_kernel<T, LOG2M, fast_c>), grid, wg, 0, s, x, x_stride, y, y_stride, t.tw_half,
+                           t.twr, t.tw4n, g, g0, batch);
       return hipGetLastError();
     };
     return fast ? go(std::true_type{}) : go(std::false_type{});

@@ -5,29 +5,15 @@
 
 namespace pdsp_host {
 
-// f(integral_constant<log2m>) for the packed sizes 5 <= log2m <= 13 (N = 64 ... 16384), the plan sizes whose packed
-// tables exist in both precisions
-template <int Lo = 5, class F>
-static hipError_t with_int_fir(int log2m, const F &f) {
-  if constexpr (Lo <= 13) {
-    if (log2m == Lo) return f(std::integral_constant<int, Lo>{});
-    return with_int_fir<Lo + 1>(log2m, f);
-  } else {
-    return hipErrorInvalidValue;
-  }
-}
-
 template <typename T, int LOG2M>
 static hipError_t launch_fir_one(bool fast, const T *x, long long len, long long x_stride, const T *h_re,
                                  const T *h_im, int p1, int hop, long long nblk, long long y_off, long long y_len, T *y,
                                  long long y_stride, const Tables<T> &t, long long items, hipStream_t s) {
-  using TR = pdsp::FftTraits<LOG2M, pdsp::packed_log2e(LOG2M)>;
-  const long long ngroups = (items + TR::ROWS - 1) / TR::ROWS;
   const T g = T(1) / T(4 << LOG2M);  // 1 / (2N)
   auto go = [&](auto fast_c) {
-    hipLaunchKernelGGL((pdsp::fir_overlap_save_kernel<T, LOG2M, fast_c>), dim3((unsigned)ngroups), dim3(TR::WG), 0, s,
-                       x, len, x_stride, h_re, h_im, p1, hop, nblk, y_off, y_len, y, y_stride, t.tw_half, t.twr, g,
-                       items);
+    hipLaunchKernelGGL((pdsp::fir_overlap_save_kernel<T, LOG2M, fast_c>), packed_grid<LOG2M>(items),
+                       dim3(pdsp::kPackedWG<LOG2M>), 0, s, x, len, x_stride, h_re, h_im, p1, hop, nblk, y_off, y_len, y,
+                       y_stride, t.tw_half, t.twr, g, items);
     return hipGetLastError();
   };
   return fast ? go(std::true_type{}) : go(std::false_type{});
@@ -43,7 +29,7 @@ int fir_filter_dev(const pdsp_plan *plan, long long batch, const T *x, long long
   const long long items = batch * nblk;
   const bool fast = (((uintptr_t)x | (uintptr_t)y) & 7) == 0 && x_stride % 2 == 0 && y_stride % 2 == 0 && hop % 2 == 0 &&
                     (y_off - p1) % 2 == 0;
-  const hipError_t e = with_int_fir(log2m, [&](auto L) {
+  const hipError_t e = with_int<5, 13>(log2m, hipErrorInvalidValue, [&](auto L) {
     return launch_fir_one<T, L>(fast, x, len, x_stride, h_re, h_im, p1, hop, nblk, y_off, y_len, y, y_stride, t, items, s);
   });
   PDSP_HIP_TRY(e);

@@ -7,28 +7,16 @@ namespace pdsp_host {
 
 int g_istft_chunk_frames = 0;  // pdsp_set_istft_chunk_frames: 0 = the default bound below
 
-// f(integral_constant<log2m>) for the packed sizes 5 <= log2m <= 13 (N = 64 ... 16384)
-template <int Lo = 5, class F>
-static hipError_t with_int_stft(int log2m, const F &f) {
-  if constexpr (Lo <= 13) {
-    if (log2m == Lo) return f(std::integral_constant<int, Lo>{});
-    return with_int_stft<Lo + 1>(log2m, f);
-  } else {
-    return hipErrorInvalidValue;
-  }
-}
-
 template <typename T>
 int stft_complex_dev(const pdsp_plan *plan, long long batch, const T *frames, long long frame_len,
                      long long frame_stride, const T *window, T *re_out, T *im_out, hipStream_t s) {
   const Tables<T> &t = tables<T>(plan);
-  const hipError_t e = with_int_stft(plan->log2n - 1, [&](auto L) {
+  const hipError_t e = with_int<5, 13>(plan->log2n - 1, hipErrorInvalidValue, [&](auto L) {
     constexpr int LOG2M = decltype(L)::value;
-    using TR = pdsp::FftTraits<LOG2M, pdsp::packed_log2e(LOG2M)>;
-    const long long ngroups = (batch + TR::ROWS - 1) / TR::ROWS;
     auto go = [&](auto win_c) {
-      hipLaunchKernelGGL((pdsp::stft_complex_kernel<T, LOG2M, win_c>), dim3((unsigned)ngroups), dim3(TR::WG), 0, s,
-                         frames, window, frame_len, frame_stride, t.tw_half, t.twr, re_out, im_out, batch);
+      hipLaunchKernelGGL((pdsp::stft_complex_kernel<T, LOG2M, win_c>), packed_grid<LOG2M>(batch),
+                         dim3(pdsp::kPackedWG<LOG2M>), 0, s, frames, window, frame_len, frame_stride, t.tw_half, t.twr,
+                         re_out, im_out, batch);
       return hipGetLastError();
     };
     return window ? go(std::true_type{}) : go(std::false_type{});
@@ -69,14 +57,13 @@ int istft_dev(const pdsp_plan *plan, long long frames, const T *re_in, const T *
   const long long n = plan->n, bins = n / 2 + 1;
   const T g = T(1) / T(n);
   auto frame_launch = [&](auto direct_c, long long first, long long items, T *dst) {
-    return with_int_stft(plan->log2n - 1, [&](auto L) {
+    return with_int<5, 13>(plan->log2n - 1, hipErrorInvalidValue, [&](auto L) {
       constexpr int LOG2M = decltype(L)::value;
-      using TR = pdsp::FftTraits<LOG2M, pdsp::packed_log2e(LOG2M)>;
-      const long long ngroups = (items + TR::ROWS - 1) / TR::ROWS;
       const T *re = re_in + (size_t)first * (size_t)bins, *im = im_in + (size_t)first * (size_t)bins;
       auto go = [&](auto win_c) {
-        hipLaunchKernelGGL((pdsp::istft_frame_kernel<T, LOG2M, win_c, direct_c>), dim3((unsigned)ngroups), dim3(TR::WG), 0,
-                           s, re, im, window, first, items, frames, hop, dst, t.tw_half, t.twr, g);
+        hipLaunchKernelGGL((pdsp::istft_frame_kernel<T, LOG2M, win_c, direct_c>), packed_grid<LOG2M>(items),
+                           dim3(pdsp::kPackedWG<LOG2M>), 0, s, re, im, window, first, items, frames, hop, dst,
+                           t.tw_half, t.twr, g);
         return hipGetLastError();
       };
       return window ? go(std::true_type{}) : go(std::false_type{});

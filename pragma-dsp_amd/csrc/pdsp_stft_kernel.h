@@ -2,18 +2,15 @@
 //
 // Forward (stft_complex_kernel): one row = one frame b of `frame_len` samples at row stride h (overlapping frames of
 // one signal are read in place, never materialised), zero-padded to N:
-//   1. z[m] = w[2m] x[2m] + i w[2m+1] x[2m+1], Z = FFT_M(z)     -- the packed-real forward of spectrum_packed_kernel;
-//   2. X[k] = (S - iP)/2, X[M-k] = conj(S + iP)/2, S = Z[k] + conj Z[M-k], P = W_N^k (Z[k] - conj Z[M-k]) -- the
-//      Hermitian split of fir_overlap_save_kernel's step 2, for the pair (k, M-k) one thread owns; X[0] and X[M]
-//      come from the pair k = 0, X[M/2] from k = M/2;
-//   3. X[k], k = 0 ... M, to the planes re / im [frame][M + 1] (unscaled: the one-sided DFT of w * frame).
+//   1. z[m] = w[2m] x[2m] + i w[2m+1] x[2m+1], Z = FFT_M(z)     -- the packed-real row of pdsp_packed.h;
+//   2. X[k] and X[M-k], half the forward split of the pair (k, M-k), k = 0 ... M, to the planes re / im
+//      [frame][M + 1] (unscaled: the one-sided DFT of w * frame).
 // HBM traffic: N/h reads (h < N: L2 serves part of the overlap) + (N + 2)/N writes per input sample.
 //
 // Inverse, one frame (istft_frame_kernel): y_b = irfft(X_b, N), the imaginary parts of X[0] and X[M] ignored:
-//   4. A = (Y[k] + conj Y[M-k]) / N, B = (Y[k] - conj Y[M-k]) / N, Z'[k] = A + i W_N^-k B (fir_overlap_save_kernel's
-//      step 4, with the bins read from HBM instead of the product in LDS), stored conjugated into the row's LDS;
-//   5. one forward pass set on conj(Z') gives conj(y[2m] + i y[2m+1]) in registers (IFFT_M = conj FFT_M conj / M);
-//   6. v[n] = w[n] y[n] in registers; then
+//   3. the inverse split of Y / N, the bins read from HBM, and the second transform (pdsp_packed.h): conj(y[2m] +
+//      i y[2m+1]) in registers;
+//   4. v[n] = w[n] y[n] in registers; then
 //      DIRECT (h >= N: frames do not overlap): out[b h + n] = v / w[n]^2 if w[n]^2 > 1e-11, else 0, and the h - N gap
 //             samples behind the frame (all but the last frame) are written as 0 -- one launch, no scratch;
 //      else:  v[n] goes to scratch row (b - first) of N values.
@@ -26,7 +23,7 @@
 //   min(S + K, F) N values, S >= K + 1: at most max(256 MiB, (2K + 1) N sizeof T) whatever F is.
 #pragma once
 
-#include "pdsp_fft_kernel.h"
+#include "pdsp_packed.h"
 
 namespace pdsp {
 
@@ -41,29 +38,17 @@ stft_complex_kernel(const T *__restrict__ frames, const T *__restrict__ win, con
                     const long long stride, const typename vec2<T>::type *__restrict__ tw,
                     const typename vec2<T>::type *__restrict__ twr, T *__restrict__ re_out, T *__restrict__ im_out,
                     const long long batch) {
-  constexpr int LOG2E = packed_log2e(LOG2M);
-  using TR = FftTraits<LOG2M, LOG2E>;
-  constexpr int E = TR::E, TP = TR::TP, M = TR::N;
-  static_assert(LOG2M >= 5 && LOG2E == 4, "packed path: TP >= 2, sixteen points per thread (W_N^(TP q) = W_32^q)");
+  using PR = PackedRow<T, LOG2M>;
+  constexpr int E = PR::E, TP = PR::TP, M = PR::M;
 
-  __shared__ cx<T> lds[TR::LDS_ELEMS];
+  __shared__ cx<T> lds[PR::TR::LDS_ELEMS];
+  const PR pr(lds, batch);
+  const int tid = pr.tid;
+  const T *const xrow = frames + (size_t)pr.row * (size_t)stride;
 
-  const int tid = (int)(threadIdx.x % TP);
-  const int rloc = (int)(threadIdx.x / TP);
-  const long long row_raw = (long long)blockIdx.x * TR::ROWS + rloc;
-  const bool live = row_raw < batch;
-  // dead rows of the last workgroup recompute the last live frame and skip the stores: every thread reaches every
-  // barrier (batch < 2^31 is checked on the host)
-  const long long row = uniform_row<TP>(live ? row_raw : batch - 1);
-  cx<T> *const lrow = lds + rloc * TR::LROW;
-  const T *const xrow = frames + (size_t)row * (size_t)stride;
-
-  constexpr bool kRegTw = TP >= 16;
-  std::conditional_t<kRegTw, RegTwiddles<T, LOG2M, LOG2E>, TableTwiddles<T, LOG2M, LOG2E>> twf;
   // tables first (load_order_fence's header): twiddle bases, the split twiddle, the thread's window values
-  if constexpr (kRegTw) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
-  else twf.tw = reinterpret_cast<const cx<T> *>(tw);
-  const cx<T> twk0 = reinterpret_cast<const cx<T> *>(twr)[(unsigned)tid];  // W_N^tid; W_N^(tid + TP q) = twk0 W_32^q
+  PackedTwiddles<T, LOG2M> twd;
+  twd.load(tw, twr, tid);
   cx<T> wv[HAS_WIN ? E : 1];
   if constexpr (HAS_WIN)  // a window at any alignment: two scalar loads per pair
     static_for<E>([&](auto q) { wv[q] = cx<T>{(win + 2 * TP * q)[2 * (unsigned)tid], (win + 2 * TP * q + 1)[2 * (unsigned)tid]}; });
@@ -79,28 +64,22 @@ stft_complex_kernel(const T *__restrict__ frames, const T *__restrict__ win, con
   });
   if constexpr (HAS_WIN) static_for<E>([&](auto q) { x[q] = x[q] * wv[q]; });
 
-  fft_passes<T, LOG2M, true, LOG2E>(x, lrow, twf, tid);  // Z in LDS, natural order
+  fft_passes<T, LOG2M, true, PR::LOG2E>(x, pr.lrow, twd.twf, tid);  // Z in LDS, natural order
   __syncthreads();
-  if (!live) return;  // no barrier below
+  if (!pr.live) return;  // no barrier below
 
-  T *const rrow = re_out + (size_t)row * (size_t)(M + 1);
-  T *const irow = im_out + (size_t)row * (size_t)(M + 1);
-  // pairs k = tid + TP q, q < E/2 (k < M/2); k = M/2 is one more pair for tid == 0 (it pairs with itself)
-  static_for<E / 2 + 1>([&](auto qc) {
-    constexpr int q = qc;
-    if (q < E / 2 || tid == 0) {
-      const int k = tid + TP * q, k2 = (M - k) & (M - 1);  // k = 0: Z[M] == Z[0]
-      const cx<T> z = lrow[lds_pad(k)], zp = lrow[lds_pad(k2)];
-      const cx<T> w = mul_w32<T, q>(twk0);  // W_N^k
-      const cx<T> sm = z + conj(zp), pm = cmul(z - conj(zp), w);
-      const cx<T> xa = add_mul_neg_i(sm, pm) * T(0.5);        // X[k]
-      const cx<T> xb = conj(add_mul_pos_i(sm, pm)) * T(0.5);  // X[M-k]  (k = 0: the Nyquist bin X[M])
-      rrow[k] = xa.x;
-      irow[k] = xa.y;
-      if (k != M / 2) {
-        rrow[M - k] = xb.x;
-        irow[M - k] = xb.y;
-      }
+  T *const rrow = re_out + (size_t)pr.row * (size_t)(M + 1);
+  T *const irow = im_out + (size_t)pr.row * (size_t)(M + 1);
+  pr.for_each_pair([&](auto q, const int k) {
+    const auto sp = pr.forward_split(k, (M - k) & (M - 1));
+    const cx<T> w = twd.wk(q);  // W_N^k
+    const cx<T> xa = sp.x(w) * T(0.5);   // X[k]
+    const cx<T> xb = sp.xm(w) * T(0.5);  // X[M-k]  (k = 0: the Nyquist bin X[M])
+    rrow[k] = xa.x;
+    irow[k] = xa.y;
+    if (k != M / 2) {
+      rrow[M - k] = xb.x;
+      irow[M - k] = xb.y;
     }
   });
 }
@@ -113,51 +92,33 @@ istft_frame_kernel(const T *__restrict__ re_in, const T *__restrict__ im_in, con
                    const long long first, const long long items, const long long nframes, const long long hop,
                    T *__restrict__ out, const typename vec2<T>::type *__restrict__ tw,
                    const typename vec2<T>::type *__restrict__ twr, const T g) {
-  constexpr int LOG2E = packed_log2e(LOG2M);
-  using TR = FftTraits<LOG2M, LOG2E>;
-  constexpr int E = TR::E, TP = TR::TP, M = TR::N;
-  static_assert(LOG2M >= 5 && LOG2E == 4, "packed path: TP >= 2, sixteen points per thread (W_N^(TP q) = W_32^q)");
+  using PR = PackedRow<T, LOG2M>;
+  constexpr int E = PR::E, TP = PR::TP, M = PR::M;
   typedef T V2 __attribute__((ext_vector_type(2)));
 
-  __shared__ cx<T> lds[TR::LDS_ELEMS];
-
-  const int tid = (int)(threadIdx.x % TP);
-  const int rloc = (int)(threadIdx.x / TP);
-  const long long item_raw = (long long)blockIdx.x * TR::ROWS + rloc;
-  const bool live = item_raw < items;
-  // dead rows recompute the last live frame and skip the stores: every thread reaches every barrier
-  const long long item = uniform_row<TP>(live ? item_raw : items - 1);
-  cx<T> *const lrow = lds + rloc * TR::LROW;
+  __shared__ cx<T> lds[PR::TR::LDS_ELEMS];
+  const PR pr(lds, items);
+  const int tid = pr.tid;
+  const long long item = pr.row;
   const T *const rrow = re_in + (size_t)item * (size_t)(M + 1);
   const T *const irow = im_in + (size_t)item * (size_t)(M + 1);
 
-  const cx<T> twk0 = reinterpret_cast<const cx<T> *>(twr)[(unsigned)tid];  // W_N^tid
-  // the inverse split, pair (k, M-k), straight from the bins into the row's LDS (every slot has one owner)
-  static_for<E / 2 + 1>([&](auto qc) {
-    constexpr int q = qc;
-    if (q < E / 2 || tid == 0) {
-      const int k = tid + TP * q, k2 = M - k;  // k = 0 pairs with the Nyquist bin M
-      cx<T> ya{rrow[k], irow[k]}, yb{rrow[k2], irow[k2]};
-      if (k == 0) ya.y = yb.y = T(0);  // irfft ignores the imaginary parts of bins 0 and M
-      ya = ya * g;
-      yb = yb * g;
-      const cx<T> w = mul_w32<T, q>(twk0);  // W_N^k
-      const cx<T> a = ya + conj(yb), c = cmul(ya - conj(yb), conj(w));  // A, W_N^-k B
-      lrow[lds_pad(k)] = conj(add_mul_pos_i(a, c));                     // conj Z'[k] / N
-      if (k != 0 && k2 != k) lrow[lds_pad(k2)] = add_mul_neg_i(a, c);   // conj Z'[M-k] / N
-    }
+  PackedTwiddles<T, LOG2M> twd;
+  twd.load_split(twr, tid);
+  // the inverse split straight from the bins
+  pr.for_each_pair([&](auto q, const int k) {
+    const int k2 = M - k;  // k = 0 pairs with the Nyquist bin M
+    cx<T> ya{rrow[k], irow[k]}, yb{rrow[k2], irow[k2]};
+    if (k == 0) ya.y = yb.y = T(0);  // irfft ignores the imaginary parts of bins 0 and M
+    ya = ya * g;
+    yb = yb * g;
+    pr.inverse_split(k, k2, ya, yb, twd.wk(q));
   });
-  constexpr bool kRegTw = TP >= 16;
-  std::conditional_t<kRegTw, RegTwiddles<T, LOG2M, LOG2E>, TableTwiddles<T, LOG2M, LOG2E>> twf;
-  if constexpr (kRegTw) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
-  else twf.tw = reinterpret_cast<const cx<T> *>(tw);
+  twd.load_passes(tw, tid);
   cx<T> x[E];
-  __syncthreads();
-  fft_pass_readback<T, LOG2M, LOG2E>(x, lrow, tid);
-  __syncthreads();  // the first pass writes LDS again
-  fft_passes<T, LOG2M, false, LOG2E>(x, lrow, twf, tid);  // conj(y[2m] + i y[2m+1]) in slot q, m = tid + TP q
+  pr.second_transform(x, twd.twf);  // conj(y[2m] + i y[2m+1]) in slot q, m = tid + TP q
 
-  if (!live) return;
+  if (!pr.live) return;
   const long long b = first + item;
   static_for<E>([&](auto q) {
     const int n = 2 * (tid + TP * q);
