@@ -476,6 +476,39 @@ PDSP_API int pdsp_dct_f64(const pdsp_plan *plan, long long batch, const double *
 /* synchronous f64 host form: `batch` contiguous rows of n values (n a power of two, 64 ... 16384) */
 PDSP_API int pdsp_dct_host_f64(const double *x, long long batch, long long n, int type, int norm, double *y);
 
+/* ---- Hilbert transform, analytic signal, envelope and instantaneous phase, f32 / f64 ----------- */
+/* The reference's roadmap v0.3 ("Hilbert / analytic signal helpers").  Conventions are scipy.signal.hilbert's for an
+ * even length: with X = rfft(x) of a real row of N samples,
+ *   Hx = irfft(Y, N),  Y[k] = -i X[k] for 0 < k < N/2,  Y[0] = Y[N/2] = 0,   a = x + i Hx == scipy.signal.hilbert(x).
+ * A row holds `len` samples, 1 <= len <= N, and is zero-padded to N (scipy.signal.hilbert(x, N=n)); every output row
+ * has N samples.  out_mode selects what one launch writes per row:
+ *   ANALYTIC  x[n], Hx[n] interleaved, 2N values (the real parts are the loaded samples bit for bit)
+ *   IMAG      Hx[n]     ENVELOPE  sqrt(x[n]^2 + Hx[n]^2)     PHASE  atan2(Hx[n], x[n])        N values each
+ * The envelope is formed as written, without scaling: it overflows where x^2 + Hx^2 does (|a| above ~1.8e19 in f32,
+ * ~1.3e154 in f64) and loses its precision, then flushes to zero, where the squares are subnormal (|a| below ~1e-19
+ * in f32, ~1.5e-154 in f64), unlike abs(scipy.signal.hilbert(x)), which is a hypot.
+ * N = pdsp_plan_size(), 64 <= N <= 16384 in both precisions (any other power of two: PDSP_ERR_UNSUPPORTED_SIZE).
+ * f32 ~1e-7 * log2 N of max|a|, f64 ~1.6e-16 * log2 N.
+ * Every argument is checked before any device work: a null plan or buffer, batch < 1, len outside 1 ... N,
+ * x_stride < len, y_stride < N (ANALYTIC: < 2N), an unknown out_mode, extents that overflow 64 bits or a grid of 2^31
+ * rows give PDSP_ERR_BAD_ARG, and so does an output whose byte extent meets the input's, except the exact in-place
+ * call y == x, y_stride == x_stride of the three N-out modes (ANALYTIC is never in place). */
+typedef enum pdsp_hilbert_out {
+  PDSP_HILBERT_ANALYTIC = 0,
+  PDSP_HILBERT_IMAG = 1,
+  PDSP_HILBERT_ENVELOPE = 2,
+  PDSP_HILBERT_PHASE = 3
+} pdsp_hilbert_out;
+/* `batch` rows of `len` samples at x_stride elements; y rows at y_stride elements */
+PDSP_API int pdsp_hilbert_f32(const pdsp_plan *plan, long long batch, const float *x, long long x_stride, long long len,
+                              int out_mode, float *y, long long y_stride, pdsp_stream stream);
+PDSP_API int pdsp_hilbert_f64(const pdsp_plan *plan, long long batch, const double *x, long long x_stride,
+                              long long len, int out_mode, double *y, long long y_stride, pdsp_stream stream);
+/* synchronous f64 host form: `batch` contiguous rows of `len` samples in, contiguous rows of n (ANALYTIC: 2n) values
+ * out (n a power of two, 64 ... 16384) */
+PDSP_API int pdsp_hilbert_host_f64(const double *x, long long batch, long long len, long long n, int out_mode,
+                                   double *y);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,10 +22,12 @@ from .filters import FirFilter, fir_filter, firFilter  # noqa: F401
 from .spectrum import SpectrumPeak, SpectrumResult, spectrum, spectrumBatch  # noqa: F401
 from .stft import istft, stft  # noqa: F401
 from .dct import dct, idct  # noqa: F401
+from .hilbert import envelope, hilbert, instantaneous_phase  # noqa: F401
 
 __all__ = [
     "ComplexArray", "Radix2Fft", "createComplexArray", "isPowerOfTwo", "nextPowerOfTwo",
     "FFT", "applyWindow", "binFrequencies", "createWindow", "fftShift", "fftShiftComplex",
     "magnitude", "phase", "spectrum", "spectrumBatch", "SpectrumPeak", "SpectrumResult", "PdspError",
     "FirFilter", "fir_filter", "firFilter", "stft", "istft", "dct", "idct",
+    "hilbert", "envelope", "instantaneous_phase",
 ]

@@ -41,6 +41,7 @@ WINDOW_TYPES = {"rect": 0, "hann": 1, "hamming": 2, "blackman": 3}
 SIDES = {"one": 0, "two": 1}
 FIR_MODES = {"full": 0, "same": 1, "valid": 2, "filter": 3}
 DCT_NORMS = {"backward": 0, "ortho": 1, "forward": 2}
+HILBERT_OUT = {"analytic": 0, "imag": 1, "envelope": 2, "phase": 3}
 COMPLEX_OPS = {"add": 0, "sub": 1, "mul": 2, "div": 3, "conj": 4, "scale": 5, "mulScalar": 6}
 
 
@@ -138,6 +139,9 @@ def _load() -> C.CDLL:
         "pdsp_dct_f32": ([vp, ll, vp, ll, i32, i32, vp, ll, vp], i32),
         "pdsp_dct_f64": ([vp, ll, vp, ll, i32, i32, vp, ll, vp], i32),
         "pdsp_dct_host_f64": ([dp, ll, ll, i32, i32, dp], i32),
+        "pdsp_hilbert_f32": ([vp, ll, vp, ll, ll, i32, vp, ll, vp], i32),
+        "pdsp_hilbert_f64": ([vp, ll, vp, ll, ll, i32, vp, ll, vp], i32),
+        "pdsp_hilbert_host_f64": ([dp, ll, ll, ll, i32, dp], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -395,6 +395,71 @@ class BatchedFft:
         swap = {"backward": "forward", "forward": "backward", None: "forward"}
         return self._dct_call(x, 5 - type, swap.get(norm, norm), out, "idct")
 
+    def _hilbert_call(self, x, mode, out, name):
+        """Validation shared by hilbert / hilbert_imag / envelope / instantaneous_phase: x [rows, len <= N] with
+        contiguous rows at any row stride (x.stride(0)); out None, a tensor [rows, N] with its own row stride (hilbert:
+        complex), or, in the N-out modes, the rows x lies in (exact in place: out begins where x does and has x's row
+        stride; x is out itself, or out[:, :len] when len < N)."""
+        n = self.size
+        analytic = mode == "analytic"
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise PdspError(_capi.ERR_BAD_ARG, f"{name}: x must be a 2-D tensor [rows, len]")
+        if x.dtype != self.dtype or not x.is_cuda or x.device != self.device:
+            raise PdspError(_capi.ERR_BAD_ARG, f"{name}: x must be a {self.dtype} tensor on {self.device}")
+        rows, ln = x.shape
+        if rows < 1:
+            raise PdspError(_capi.ERR_BAD_ARG, "batch must be >= 1, got 0")
+        if ln < 1 or ln > n:
+            raise PdspError(_capi.ERR_BAD_ARG, f"len must be 1 ... N = {n}, got {ln}")
+        if rows > 1 and x.stride(0) < ln or (ln > 1 and x.stride(1) != 1):
+            raise PdspError(_capi.ERR_BAD_ARG, f"{name}: x needs contiguous rows at a row stride >= len")
+        odt = self.dtype
+        if analytic:
+            odt = torch.complex64 if self.dtype == torch.float32 else torch.complex128
+        k = 2 if analytic else 1  # plan-dtype values per output element
+        if out is None:
+            out = torch.empty((rows, n), dtype=odt, device=self.device)
+        else:
+            if not isinstance(out, torch.Tensor) or out.dim() != 2:
+                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: out must be a 2-D tensor [rows, N]")
+            if out.dtype != odt or not out.is_cuda or out.device != self.device:
+                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: out must be a {odt} tensor on {self.device}")
+            if tuple(out.shape) != (rows, n):
+                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: out {tuple(out.shape)} must be [{rows}, {n}]")
+            if rows > 1 and out.stride(0) < n or out.stride(1) != 1:
+                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: out needs contiguous rows at a row stride >= N")
+        xs = x.stride(0) if rows > 1 else max(ln, n)
+        ys = k * out.stride(0) if rows > 1 else k * n
+        if out.data_ptr() == x.data_ptr() and not analytic:
+            if rows > 1 and ys != xs:
+                raise PdspError(_capi.ERR_BAD_ARG,
+                                "output overlaps input (only y == x with y_stride == x_stride may share bytes)")
+            ys = xs
+        check(getattr(lib, "pdsp_hilbert_" + self._sfx)(self._h, rows, _ptr(x), xs, ln, _capi.HILBERT_OUT[mode],
+                                                        _ptr(out), ys, _stream_ptr(self.device)))
+        return out
+
+    def hilbert(self, x: torch.Tensor, out: torch.Tensor | None = None):
+        """scipy.signal.hilbert(x, N=self.size, axis=-1): the analytic signal x + i Hx of the rows of x
+        [rows, len <= N] (zero-padded to N), a complex tensor [rows, N], one launch.  torch.view_as_real(result) is
+        the interleaved buffer the kernel wrote; its real parts are x bit for bit.  Never in place.
+        64 <= N <= 16384."""
+        return self._hilbert_call(x, "analytic", out, "hilbert")
+
+    def hilbert_imag(self, x: torch.Tensor, out: torch.Tensor | None = None):
+        """The Hilbert transform Hx = imag(scipy.signal.hilbert(x, N)) of the rows of x, [rows, N], one launch;
+        out=x runs in place (len < N: x = out[:, :len])."""
+        return self._hilbert_call(x, "imag", out, "hilbert_imag")
+
+    def envelope(self, x: torch.Tensor, out: torch.Tensor | None = None):
+        """abs(scipy.signal.hilbert(x, N)) of the rows of x, [rows, N], one launch; out=x runs in place."""
+        return self._hilbert_call(x, "envelope", out, "envelope")
+
+    def instantaneous_phase(self, x: torch.Tensor, out: torch.Tensor | None = None):
+        """angle(scipy.signal.hilbert(x, N)) of the rows of x in (-pi, pi], not unwrapped, [rows, N], one launch;
+        out=x runs in place."""
+        return self._hilbert_call(x, "phase", out, "instantaneous_phase")
+
     def spectrum_peaks(self, frames: torch.Tensor, window="rect", sides: str = "one", sample_rate: float = 1.0,
                        want_amp: bool = False, want_phase: bool = False):
         """Rows of the whole spectrum() tail on the device: one SpectrumPeak per frame

@@ -1877,3 +1877,90 @@ int pdsp_dct_host_f64(const double *x, long long batch, long long n, int type, i
   PDSP_HIP_TRY(hipMemcpy(y, sc.d, nx * sizeof(double), hipMemcpyDeviceToHost));
   return PDSP_OK;
 }
+
+/* ---- Hilbert transform, analytic signal, envelope and phase ---------------- */
+
+namespace pdsp_host {
+
+int check_hilbert_mode(int out_mode) {
+  if (out_mode < PDSP_HILBERT_ANALYTIC || out_mode > PDSP_HILBERT_PHASE)
+    return fail(PDSP_ERR_BAD_ARG, "Hilbert output must be 0 (analytic), 1 (imag), 2 (envelope) or 3 (phase), got %d",
+                out_mode);
+  return PDSP_OK;
+}
+
+template <typename T>
+int hilbert_t(const pdsp_plan *plan, long long batch, const T *x, long long x_stride, long long len, int out_mode, T *y,
+              long long y_stride, hipStream_t s) {
+  if (int rc = check_packed_plan<T>(plan, "the Hilbert transform", false)) return rc;
+  const long long n = plan->n;
+  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
+  if (len < 1 || len > n) return fail(PDSP_ERR_BAD_ARG, "len must be 1 ... N = %lld, got %lld", n, len);
+  if (int rc = check_hilbert_mode(out_mode)) return rc;
+  const long long yn = out_mode == PDSP_HILBERT_ANALYTIC ? 2 * n : n;  // values per output row
+  if (x_stride < len || y_stride < yn)
+    return fail(PDSP_ERR_BAD_ARG, "strides must be >= len = %lld (x) and >= %lld (y), got x_stride %lld, y_stride %lld",
+                len, yn, x_stride, y_stride);
+  long long xc = 0, yc = 0;
+  if (!mad_ok(batch - 1, x_stride, len, &xc) || !mad_ok(batch - 1, y_stride, yn, &yc) || xc > (LLONG_MAX / 8) ||
+      yc > (LLONG_MAX / 8))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+  if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  // exact in place is safe in the N-out modes (a row is loaded in full by its own workgroup before that workgroup's
+  // first barrier, and a thread stores only to the samples it has just re-read); any other overlap would let one
+  // row's stores reach another row's loads, and ANALYTIC writes two values per sample
+  const bool in_place =
+      out_mode != PDSP_HILBERT_ANALYTIC && (const void *)x == (const void *)y && x_stride == y_stride;
+  if (!in_place && host_ranges_overlap(y, (size_t)yc * sizeof(T), x, (size_t)xc * sizeof(T)))
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only y == x with y_stride == x_stride may share bytes, and "
+                                  "not in analytic mode)");
+  DeviceGuard dg(plan->device);
+  PDSP_HIP_TRY(dg.err);
+  return hilbert_dev<T>(plan, batch, x, x_stride, len, out_mode, y, y_stride, s);
+}
+
+}  // namespace pdsp_host
+
+int pdsp_hilbert_f32(const pdsp_plan *plan, long long batch, const float *x, long long x_stride, long long len,
+                     int out_mode, float *y, long long y_stride, pdsp_stream stream) {
+  return hilbert_t<float>(plan, batch, x, x_stride, len, out_mode, y, y_stride, (hipStream_t)stream);
+}
+int pdsp_hilbert_f64(const pdsp_plan *plan, long long batch, const double *x, long long x_stride, long long len,
+                     int out_mode, double *y, long long y_stride, pdsp_stream stream) {
+  return hilbert_t<double>(plan, batch, x, x_stride, len, out_mode, y, y_stride, (hipStream_t)stream);
+}
+
+int pdsp_hilbert_host_f64(const double *x, long long batch, long long len, long long n, int out_mode, double *y) {
+  if (!pdsp_is_pow2(n)) return fail(PDSP_ERR_SIZE_NOT_POW2, "FFT size must be power of two, got %lld", n);
+  if (n < 64 || n > 16384)
+    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "the Hilbert transform needs a plan of 64 <= N <= 16384, got %lld", n);
+  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
+  if (len < 1 || len > n) return fail(PDSP_ERR_BAD_ARG, "len must be 1 ... N = %lld, got %lld", n, len);
+  if (int rc = check_hilbert_mode(out_mode)) return rc;
+  const long long yn = out_mode == PDSP_HILBERT_ANALYTIC ? 2 * n : n;
+  long long xcount = 0, ycount = 0;
+  if (batch > 0x7fffffffLL || !mad_ok(batch, len, 0, &xcount) || !mad_ok(batch, yn, 0, &ycount) || ycount > (1LL << 40))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x %lld overflows", batch, n);
+  if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  if (int rc = require_device()) return rc;
+  CachedPlan cp;
+  if (int rc = cached_plan(n, &cp)) return rc;
+  pdsp_plan *const plan = cp.plan;
+  std::lock_guard<std::mutex> lk(plan->mu);
+  DeviceGuard g(plan->device);
+  PDSP_HIP_TRY(g.err);
+  if (!plan->stream) PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
+  const hipStream_t s = plan->stream;
+  // rows of n values on the device whatever len is (the wide path's layout), x behind y
+  const size_t ny = (size_t)ycount, nx = (size_t)(batch * n);
+  HostDeviceBuf sc;
+  PDSP_HIP_TRY(hipMalloc((void **)&sc.d, (ny + nx) * sizeof(double)));
+  double *const dy = sc.d, *const dx = sc.d + ny;
+  PDSP_HIP_TRY(hipMemcpy2DAsync(dx, (size_t)n * sizeof(double), x, (size_t)len * sizeof(double),
+                                (size_t)len * sizeof(double), (size_t)batch, hipMemcpyHostToDevice, s));
+  if (int rc = hilbert_t<double>(plan, batch, dx, n, len, out_mode, dy, yn, s)) return rc;
+  PDSP_HIP_TRY(hipStreamSynchronize(s));
+  PDSP_HIP_TRY(hipMemcpy(y, dy, ny * sizeof(double), hipMemcpyDeviceToHost));
+  return PDSP_OK;
+}

@@ -1,6 +1,6 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from seven translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from eight translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
@@ -10,6 +10,7 @@
 //   pdsp_kernels_fir.hip          FIR filtering (fused overlap-save) and the filter spectrum, f32 and f64
 //   pdsp_kernels_stft.hip         complex STFT and its overlap-add inverse, f32 and f64
 //   pdsp_kernels_dct.hip          DCT-II and DCT-III, f32 and f64
+//   pdsp_kernels_hilbert.hip      Hilbert transform, analytic signal, envelope and phase, f32 and f64
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -311,5 +312,16 @@ int dct_dev(const pdsp_plan *plan, long long batch, const T *x, long long x_stri
             long long y_stride, hipStream_t s);
 // the 16-byte path's condition: both row pointers 16-byte aligned, both strides multiples of 16 bytes
 bool dct_fast_path(const void *x, long long x_stride, const void *y, long long y_stride, size_t elem);
+
+// pdsp_hilbert_* after validation (pdsp_kernels_hilbert.hip): 64 <= N <= 16384, 1 <= batch < 2^31, 1 <= len <= N,
+// x_stride >= len, y_stride >= N (ANALYTIC: 2N), out_mode a pdsp_hilbert_out.  y == x with y_stride == x_stride is
+// allowed in the three N-out modes (exact in place), no other overlap.
+template <typename T>
+int hilbert_dev(const pdsp_plan *plan, long long batch, const T *x, long long x_stride, long long len, int out_mode,
+                T *y, long long y_stride, hipStream_t s);
+// the wide path's condition: len == N, x rows aligned to 2 elements with an even stride, y rows aligned to 2 elements
+// (ANALYTIC: to 16 bytes) with a stride that keeps that
+bool hilbert_fast_path(const void *x, long long x_stride, long long len, long long n, int out_mode, const void *y,
+                       long long y_stride, size_t elem);
 
 }  // namespace pdsp_host

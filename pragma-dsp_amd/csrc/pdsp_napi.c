@@ -637,6 +637,28 @@ static napi_value Dct(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* hilbert(mode, n, x, y): y receives n values (mode 0, analytic: 2n, interleaved) of one signal of x.length <= n
+ * samples zero-padded to n (mode a pdsp_hilbert_out).  The integers are read first and the two typed-array pointers
+ * last, as in dct().  A size the library refuses reaches it unchanged (it fails before touching y), so its message is
+ * what the caller sees. */
+static napi_value Hilbert(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return NULL;
+  int64_t mode, n;
+  double *x, *y;
+  size_t nx, ny;
+  if (!get_i64(env, argv[0], &mode) || !get_i64(env, argv[1], &n) || !f64_array(env, argv[2], &x, &nx) ||
+      !f64_array(env, argv[3], &y, &ny))
+    return NULL;
+  if (mode < INT32_MIN || mode > INT32_MAX) mode = -1; /* refused by the library as an unknown output */
+  if (n >= 64 && n <= 16384 && (int64_t)ny < (mode == PDSP_HILBERT_ANALYTIC ? 2 * n : n)) {
+    napi_throw_error(env, NULL, "pdsp_napi: hilbert output too small");
+    return NULL;
+  }
+  if (pdsp_hilbert_host_f64(x, 1, (long long)nx, (long long)n, (int)mode, y) != PDSP_OK) return throw_pdsp(env);
+  return NULL;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   const struct {
     const char *name;
@@ -649,7 +671,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"spectrumBatch", SpectrumBatch}, {"spectrumRows", SpectrumRows},
       {"nextPow2", NextPow2},     {"deviceCount", DeviceCount},
       {"firFilter", FirFilter},   {"stft", Stft},               {"istft", Istft},
-      {"dct", Dct},
+      {"dct", Dct},                 {"hilbert", Hilbert},
   };
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
     napi_value f;

@@ -4,6 +4,7 @@ import * as fourierNs from './fourier';
 import * as filtersNs from './filters';
 import * as stftNs from './stft';
 import * as dctNs from './dct';
+import * as hilbertNs from './hilbert';
 
 export { spectrum, spectrumBatch, spectrumStream, SpectrumOptions, SpectrumPeak, SpectrumResult } from './spectrum';
 export { ComplexArray } from './core';
@@ -11,6 +12,7 @@ export { WindowType } from './fourier';
 export { FirMode, FirFilterOptions } from './filters';
 export { StftWindow, StftOptions, StftResult } from './stft';
 export { DctType, DctNorm, DctOptions } from './dct';
+export { HilbertOptions, AnalyticSignal } from './hilbert';
 
 export const core: {
   createComplexArray: typeof coreNs.createComplexArray;
@@ -38,4 +40,9 @@ export const stft: {
 export const dct: {
   dct: typeof dctNs.dct;
   idct: typeof dctNs.idct;
+};
+export const hilbert: {
+  hilbert: typeof hilbertNs.hilbert;
+  envelope: typeof hilbertNs.envelope;
+  instantaneousPhase: typeof hilbertNs.instantaneousPhase;
 };

@@ -6,12 +6,14 @@
 //   require('.../js').filters    -> pragma-dsp/filters (ROADMAP.md, "Filters and utilities")
 //   require('.../js').stft       -> pragma-dsp/xform/stft (ROADMAP.md, "A) STFT")
 //   require('.../js').dct        -> pragma-dsp/xform/dct (ROADMAP.md, v0.3)
+//   require('.../js').hilbert    -> the Hilbert / analytic signal helpers (ROADMAP.md, v0.3)
 const core = require('./core');
 const fourier = require('./fourier');
 const s = require('./spectrum');
 const filters = require('./filters');
 const stft = require('./stft');
 const dct = require('./dct');
+const hilbert = require('./hilbert');
 
 module.exports = {
   spectrum: s.spectrum,
@@ -48,5 +50,10 @@ Object.defineProperty(module.exports, 'stft', {
 // pragma-dsp/xform/dct: planned by the reference (ROADMAP.md, v0.3), not enumerated for the same reason.
 Object.defineProperty(module.exports, 'dct', {
   value: { dct: dct.dct, idct: dct.idct },
+  enumerable: false,
+});
+// Hilbert / analytic signal helpers: planned by the reference (ROADMAP.md, v0.3), not enumerated for the same reason.
+Object.defineProperty(module.exports, 'hilbert', {
+  value: { hilbert: hilbert.hilbert, envelope: hilbert.envelope, instantaneousPhase: hilbert.instantaneousPhase },
   enumerable: false,
 });
