@@ -2,8 +2,9 @@
 // reference's error texts, plan objects, kernel dispatch by size, and the
 // synchronous host-f64 entry points the JS drop-in binds.
 //
-// Host side only: no kernel is instantiated in this translation unit (the dispatchers it calls -- run_complex,
-// spectrum_impl, ... -- are declared in pdsp_internal.h and live in the pdsp_kernels_*.hip units).
+// Host side only, one of the library's eight translation units: no kernel is instantiated here (the dispatchers it
+// calls -- run_complex, spectrum_impl, ... -- are declared in pdsp_internal.h and live in the seven
+// pdsp_kernels_*.hip units).
 //
 // Product path only: nothing here touches oracle/, and there is no CPU fallback --
 // without a HIP device every compute entry point fails with PDSP_ERR_DEVICE.
@@ -21,6 +22,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "pdsp_internal.h"
@@ -108,8 +110,14 @@ std::vector<T2> build_twiddles(int log2n, int log2e = 4) {
   return tw;
 }
 
-int ensure_stage(pdsp_plan *plan, size_t bytes) {
+// The plan's own stream, created on first use.  Caller holds plan->mu.
+int ensure_plan_stream(pdsp_plan *plan) {
   if (!plan->stream) PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
+  return PDSP_OK;
+}
+
+int ensure_stage(pdsp_plan *plan, size_t bytes) {
+  if (int rc = ensure_plan_stream(plan)) return rc;
   if (plan->h_bytes < bytes) {
     if (plan->h_stage) (void)hipHostFree(plan->h_stage);
     plan->h_stage = nullptr;
@@ -251,6 +259,22 @@ void trim_stage(pdsp_plan *plan) {
   }
 }
 
+// The one place a plan table reaches the device: allocate, copy, record the allocation with its owner
+// (Tables::release() frees that list, so a failure half way through a plan leaves nothing behind once the plan is
+// released), store the pointer.  A failed copy frees its allocation at once: a retried plan_window does not pile up.
+template <typename T, typename E, typename D>
+hipError_t upload_table(Tables<T> &t, const std::vector<E> &host, D **out) {
+  void *d = nullptr;
+  if (hipError_t e = hipMalloc(&d, host.size() * sizeof(E))) return e;
+  if (hipError_t e = hipMemcpy(d, host.data(), host.size() * sizeof(E), hipMemcpyHostToDevice)) {
+    (void)hipFree(d);
+    return e;
+  }
+  t.owned.push_back(d);
+  *out = (D *)d;
+  return hipSuccess;
+}
+
 // Device copy of createWindow(type, N), built once per plan and precision (the window is
 // always computed in f64 on the host and rounded once).  Caller holds plan->mu.
 template <typename T>
@@ -259,15 +283,8 @@ int plan_window(pdsp_plan *plan, int type, const T **out) {
   if (!t.win[type]) {
     std::vector<double> w((size_t)plan->n);
     if (int rc = pdsp_window_make(type, plan->n, w.data())) return rc;
-    std::vector<T> wt(w.begin(), w.end());
-    T *d = nullptr;
-    PDSP_HIP_TRY(hipMalloc((void **)&d, wt.size() * sizeof(T)));
-    hipError_t e = hipMemcpy(d, wt.data(), wt.size() * sizeof(T), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(d);
-      PDSP_HIP_TRY(e);
-    }
-    t.win[type] = d;
+    if (hipError_t e = upload_table(t, std::vector<T>(w.begin(), w.end()), &t.win[type]))
+      return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the window table", (int)e, hipGetErrorString(e));
   }
   *out = t.win[type];
   return PDSP_OK;
@@ -285,190 +302,140 @@ int host_precision() {
   return g_host_precision;
 }
 
+// Appends `count` pairs (cos, sin) of angle(k), k = 0 ... count - 1, evaluated in f64 and rounded once (P: a T2, or
+// float2 for the flat float pair tables).  Every caller spells its angle out as the kernels' derivations do:
+// (-2 pi k) / N and f * 4096 * i do not round like a normalised form of the same angle, and the tables are pinned bit
+// for bit.
+template <typename P, class Angle>
+void add_cos_sin(std::vector<P> &w, size_t count, Angle angle) {
+  w.reserve(w.size() + count);
+  for (size_t k = 0; k < count; ++k) {
+    const double a = angle(k);
+    P v;
+    v.x = (decltype(v.x))std::cos(a);
+    v.y = (decltype(v.y))std::sin(a);
+    w.push_back(v);
+  }
+}
+
+// `tw` of the N2-point rows, and the split kernels' W_N2^k for rows of 16384 and 8192 points
+template <typename T>
+hipError_t upload_transform_tables(Tables<T> &t) {
+  using T2 = typename pdsp::vec2<T>::type;
+  if (hipError_t e = upload_table(t, build_twiddles<T2>(t.log2n2), &t.tw)) return e;
+  std::vector<T2> w;
+  if (t.log2n2 == 14) {  // fft_split4_kernel: W_16384^k, k < 768
+    add_cos_sin(w, 768, [](size_t k) { return (-2.0 * M_PI * (double)k) / 16384.0; });
+    return upload_table(t, w, &t.tws4);
+  }
+  if (t.log2n2 == 13) {  // fft_split2_kernel: W_8192^k, k < 256
+    add_cos_sin(w, 256, [](size_t k) { return (-2.0 * M_PI * (double)k) / 8192.0; });
+    return upload_table(t, w, &t.tws2);
+  }
+  return hipSuccess;
+}
+
+// Radix tables of the balanced factors of a 2^lg-point transform in tile passes: two factors up to 2^18 (2^18 =
+// 512 * 512), three above; ascending, so that the widest tiles serve the passes with two strided streams
+template <typename T>
+hipError_t upload_factor_tables(Tables<T> &t, int lg, int *np, int *l, typename pdsp::vec2<T>::type **tw) {
+  if (lg <= 18) {
+    *np = 2;
+    l[0] = lg / 2, l[1] = lg - l[0];
+  } else {
+    *np = 3;
+    three_factors(lg, l);
+  }
+  for (int i = 0; i < *np; ++i)
+    if (hipError_t e = upload_table(t, build_twiddles<typename pdsp::vec2<T>::type>(l[i]), &tw[i])) return e;
+  return hipSuccess;
+}
+
+// The multi-pass paths (N beyond the single-pass limit): W_N^m = twa[m >> 9] * twb[m & 511], the tile passes of the
+// f32 transform and of the packed-real spectrum's N/2-point transform, and the general four-step path's row table
+template <typename T>
+hipError_t upload_multipass_tables(Tables<T> &t, int log2n, long long size) {
+  using T2 = typename pdsp::vec2<T>::type;
+  std::vector<T2> a, b;
+  add_cos_sin(a, (size_t)(size >> 9), [&](size_t i) { return (-2.0 * M_PI * (double)(i << 9)) / (double)size; });
+  add_cos_sin(b, 512, [&](size_t i) { return (-2.0 * M_PI * (double)i) / (double)size; });
+  if (hipError_t e = upload_table(t, a, &t.twa)) return e;
+  if (hipError_t e = upload_table(t, b, &t.twb)) return e;
+  if (sizeof(T) == 4 && log2n >= 15 && log2n <= 27) {  // tile passes (tile_pass_kernel's header)
+    // tile_cols512_kernel / tile_rows512_kernel run a 512-point factor as two 256-point halves
+    if (hipError_t e = upload_table(t, build_twiddles<T2>(8), &t.tw8)) return e;
+    if (hipError_t e = upload_factor_tables(t, log2n, &t.tp_np, t.tp_l, t.tp_tw)) return e;
+    // the N/2-point transform of the packed-real spectrum path (at 2^18 = 512 * 512 the packed first pass on
+    // 16-column tiles still reads 128-byte segments, eight samples per lane)
+    if (hipError_t e = upload_factor_tables(t, log2n - 1, &t.hp_np, t.hp_l, t.hp_tw)) return e;
+    // fused createWindow on the packed first pass (tile_pass_kernel IN = 5 / 6; fourier.ts:14-52:
+    // f = 2 pi / (size - 1)): cs(f n) by angle addition, tables built in f64.  The kernels index the parts by their
+    // sizes (TileGeom::wa ...): wa | wb | wstep | we | wq (fft_split4_kernel's packed loader, N = 2^15)
+    const double f = 2.0 * M_PI / (double)(size - 1);
+    const long long in_stride = (size / 2) >> t.hp_l[0];  // points between the rows of a column
+    const int spi = 1024 / tile_width(t.hp_l[0]);         // tile_pass_kernel's SPI
+    t.hp_win_a = (size_t)((size / 8 + 511) / 512);
+    std::vector<float2> w;
+    add_cos_sin(w, t.hp_win_a, [&](size_t i) { return f * 4096.0 * (double)i; });
+    add_cos_sin(w, 512, [&](size_t j) { return f * 8.0 * (double)j; });
+    add_cos_sin(w, 8, [&](size_t ic) { return f * 2.0 * (double)in_stride * (double)spi * (double)ic; });
+    add_cos_sin(w, 8, [&](size_t ee) { return f * (double)ee; });
+    add_cos_sin(w, 16, [&](size_t q) { return f * 2048.0 * (double)q; });
+    if (hipError_t e = upload_table(t, w, &t.hp_win)) return e;
+  }
+  if (t.log2n1 > pdsp::kMaxLog2N1) return upload_table(t, build_twiddles<T2>(t.log2n1), &t.tw1);
+  return hipSuccess;
+}
+
+// The packed-real paths (64 <= N, N/2 single-pass): radix table of the N/2-point transform, the split twiddles
+// W_N^k, 0 <= k <= N/4, and up to N = 16384 the DCT twiddles W_4N^k, 0 <= k <= N/2
+template <typename T>
+hipError_t upload_packed_tables(Tables<T> &t, int log2n, long long size) {
+  using T2 = typename pdsp::vec2<T>::type;
+  if (hipError_t e = upload_table(t, build_twiddles<T2>(log2n - 1, pdsp::packed_log2e(log2n - 1)), &t.tw_half)) return e;
+  std::vector<T2> twr, tw4;
+  add_cos_sin(twr, (size_t)(size / 4 + 1), [&](size_t k) { return (-2.0 * M_PI * (double)k) / (double)size; });
+  if (hipError_t e = upload_table(t, twr, &t.twr)) return e;
+  if (log2n > 14) return hipSuccess;
+  add_cos_sin(tw4, (size_t)(size / 2 + 1), [&](size_t k) { return (-M_PI * (double)k) / (2.0 * (double)size); });
+  return upload_table(t, tw4, &t.tw4n);
+}
+
+// Fused createWindow of the f32 single-pass spectrum kernels (fourier.ts:14-52: f = 2 pi / (size - 1)), angle-addition
+// tables built in f64: a frame on `tp` threads takes sample n = (2 tid + e) + 2 tp q, so wf_base holds cs(f (2 tid + e))
+// and wf_step cs(f 2 tp q), q < 16.  N = 16384 (spectrum_dif16k_kernel, 256 threads) has 16 more steps, at + 8192.
+hipError_t upload_fused_window_tables(Tables<float> &t, int tp, long long size) {
+  const double f = 2.0 * M_PI / (double)(size - 1);
+  std::vector<float2> base, step;
+  add_cos_sin(base, 2 * (size_t)tp, [&](size_t n) { return f * (double)n; });
+  add_cos_sin(step, 16, [&](size_t q) { return f * 2.0 * tp * (double)q; });
+  if (size == 16384) add_cos_sin(step, 16, [&](size_t q) { return f * (double)(2 * tp * (long long)q + 8192); });
+  if (hipError_t e = upload_table(t, base, &t.wf_base)) return e;
+  return upload_table(t, step, &t.wf_step);
+}
+
+// full: the N-point complex transform exists in this precision; half: so do the packed-real paths (pdsp_plan_create)
 template <typename T>
 hipError_t upload_tables(Tables<T> &t, int log2n, long long size, bool full, bool half) {
   using T2 = typename pdsp::vec2<T>::type;
-  hipError_t e = hipSuccess;
   if (full) {
     t.log2n2 = log2n > max_log2n<T>() ? max_log2n<T>() : log2n;
     t.log2n1 = log2n - t.log2n2;
-    const std::vector<T2> tw = build_twiddles<T2>(t.log2n2);
-    e = hipMalloc((void **)&t.tw, tw.size() * sizeof(T2));
-    if (e == hipSuccess) e = hipMemcpy(t.tw, tw.data(), tw.size() * sizeof(T2), hipMemcpyHostToDevice);
-    if (e == hipSuccess && t.log2n2 == 14) {  // fft_split4_kernel: 4096-point radix table + W_16384^k
-      const std::vector<T2> t12 = build_twiddles<T2>(12);
-      std::vector<T2> w(768);
-      for (size_t k = 0; k < w.size(); ++k) {
-        const double angle = (-2.0 * M_PI * (double)k) / 16384.0;
-        w[k].x = (T)std::cos(angle);
-        w[k].y = (T)std::sin(angle);
-      }
-      e = hipMalloc((void **)&t.tw12, t12.size() * sizeof(T2));
-      if (e == hipSuccess) e = hipMemcpy(t.tw12, t12.data(), t12.size() * sizeof(T2), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMalloc((void **)&t.tws4, w.size() * sizeof(T2));
-      if (e == hipSuccess) e = hipMemcpy(t.tws4, w.data(), w.size() * sizeof(T2), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && t.log2n2 == 13) {  // fft_split2_kernel: 4096-point radix table + W_8192^k
-      const std::vector<T2> t12 = build_twiddles<T2>(12);
-      std::vector<T2> w(256);
-      for (size_t k = 0; k < w.size(); ++k) {
-        const double angle = (-2.0 * M_PI * (double)k) / 8192.0;
-        w[k].x = (T)std::cos(angle);
-        w[k].y = (T)std::sin(angle);
-      }
-      e = hipMalloc((void **)&t.tw12, t12.size() * sizeof(T2));
-      if (e == hipSuccess) e = hipMemcpy(t.tw12, t12.data(), t12.size() * sizeof(T2), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMalloc((void **)&t.tws2, w.size() * sizeof(T2));
-      if (e == hipSuccess) e = hipMemcpy(t.tws2, w.data(), w.size() * sizeof(T2), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && t.log2n1 > 0) {  // W_N^m = twa[m >> 9] * twb[m & 511]
-      std::vector<T2> a((size_t)(size >> 9)), b(512);
-      for (size_t i = 0; i < a.size(); ++i) {
-        const double angle = (-2.0 * M_PI * (double)(i << 9)) / (double)size;
-        a[i].x = (T)std::cos(angle);
-        a[i].y = (T)std::sin(angle);
-      }
-      for (size_t i = 0; i < 512; ++i) {
-        const double angle = (-2.0 * M_PI * (double)i) / (double)size;
-        b[i].x = (T)std::cos(angle);
-        b[i].y = (T)std::sin(angle);
-      }
-      e = hipMalloc((void **)&t.twa, a.size() * sizeof(T2));
-      if (e == hipSuccess) e = hipMemcpy(t.twa, a.data(), a.size() * sizeof(T2), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMalloc((void **)&t.twb, b.size() * sizeof(T2));
-      if (e == hipSuccess) e = hipMemcpy(t.twb, b.data(), b.size() * sizeof(T2), hipMemcpyHostToDevice);
-      // tile passes, balanced factors (tile_pass_kernel's header), ascending so that the widest tiles
-      // serve the passes with two strided streams
-      if (e == hipSuccess && sizeof(T) == 4 && log2n >= 15 && log2n <= 27) {
-        if (log2n <= 18) {  // 2^18 = 512 * 512: both factors on 32-wide tiles (tile_cols512_kernel, tile_rows512_kernel)
-          t.tp_np = 2;
-          t.tp_l[0] = log2n / 2, t.tp_l[1] = log2n - t.tp_l[0];
-        } else {
-          t.tp_np = 3;
-          three_factors(log2n, t.tp_l);
-        }
-        if (e == hipSuccess) {
-          const std::vector<T2> t8 = build_twiddles<T2>(8);
-          e = hipMalloc((void **)&t.tw8, t8.size() * sizeof(T2));
-          if (e == hipSuccess) e = hipMemcpy(t.tw8, t8.data(), t8.size() * sizeof(T2), hipMemcpyHostToDevice);
-        }
-        for (int i = 0; i < t.tp_np && e == hipSuccess; ++i) {
-          const std::vector<T2> tf = build_twiddles<T2>(t.tp_l[i]);
-          e = hipMalloc((void **)&t.tp_tw[i], tf.size() * sizeof(T2));
-          if (e == hipSuccess) e = hipMemcpy(t.tp_tw[i], tf.data(), tf.size() * sizeof(T2), hipMemcpyHostToDevice);
-        }
-        // the N/2-point transform of the packed-real spectrum path: 2^14 ... 2^18 in two factors (2^18 = 512 * 512:
-        // the packed first pass on 16-column tiles still reads 128-byte segments, eight samples per lane), above in three
-        const int lm = log2n - 1;
-        if (lm <= 18) {
-          t.hp_np = 2;
-          t.hp_l[0] = lm / 2, t.hp_l[1] = lm - t.hp_l[0];
-        } else {
-          t.hp_np = 3;
-          three_factors(lm, t.hp_l);
-        }
-        for (int i = 0; i < t.hp_np && e == hipSuccess; ++i) {
-          const std::vector<T2> tf = build_twiddles<T2>(t.hp_l[i]);
-          e = hipMalloc((void **)&t.hp_tw[i], tf.size() * sizeof(T2));
-          if (e == hipSuccess) e = hipMemcpy(t.hp_tw[i], tf.data(), tf.size() * sizeof(T2), hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) {
-          // fused createWindow on the packed first pass (tile_pass_kernel IN = 5 / 6; fourier.ts:14-52:
-          // f = 2 pi / (size - 1)): cs(f n) by angle addition, tables built in f64
-          const double f = 2.0 * M_PI / (double)(size - 1);
-          const long long in_stride = (size / 2) >> t.hp_l[0];              // points between the rows of a column
-          const int spi = 1024 / tile_width(t.hp_l[0]);                     // tile_pass_kernel's SPI
-          t.hp_win_a = (size_t)((size / 8 + 511) / 512);
-          std::vector<float> w(2 * (t.hp_win_a + 512 + 8 + 8 + 16));  // + wq (fft_split4_kernel's packed loader, N = 2^15)
-          size_t o = 0;
-          for (size_t i = 0; i < t.hp_win_a; ++i, o += 2)
-            w[o] = (float)std::cos(f * 4096.0 * (double)i), w[o + 1] = (float)std::sin(f * 4096.0 * (double)i);
-          for (int j = 0; j < 512; ++j, o += 2) w[o] = (float)std::cos(f * 8.0 * j), w[o + 1] = (float)std::sin(f * 8.0 * j);
-          for (int ic = 0; ic < 8; ++ic, o += 2) {
-            const double a = f * 2.0 * (double)in_stride * (double)spi * (double)ic;
-            w[o] = (float)std::cos(a), w[o + 1] = (float)std::sin(a);
-          }
-          for (int ee = 0; ee < 8; ++ee, o += 2) w[o] = (float)std::cos(f * ee), w[o + 1] = (float)std::sin(f * ee);
-          for (int q = 0; q < 16; ++q, o += 2) w[o] = (float)std::cos(f * 2048.0 * q), w[o + 1] = (float)std::sin(f * 2048.0 * q);
-          e = hipMalloc((void **)&t.hp_win, w.size() * sizeof(float));
-          if (e == hipSuccess) e = hipMemcpy(t.hp_win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice);
-        }
-      }
-      if (e == hipSuccess && t.log2n1 > pdsp::kMaxLog2N1) {
-        const std::vector<T2> t1 = build_twiddles<T2>(t.log2n1);
-        e = hipMalloc((void **)&t.tw1, t1.size() * sizeof(T2));
-        if (e == hipSuccess) e = hipMemcpy(t.tw1, t1.data(), t1.size() * sizeof(T2), hipMemcpyHostToDevice);
-      }
-    }
+    if (hipError_t e = upload_transform_tables(t)) return e;
+    if (t.log2n1 > 0)
+      if (hipError_t e = upload_multipass_tables(t, log2n, size)) return e;
   }
-  if (e == hipSuccess && half) {
-    const std::vector<T2> twh = build_twiddles<T2>(log2n - 1, pdsp::packed_log2e(log2n - 1));
-    std::vector<T2> twr((size_t)(size / 4 + 1));
-    for (long long k = 0; k <= size / 4; ++k) {
-      const double angle = (-2.0 * M_PI * (double)k) / (double)size;
-      twr[(size_t)k].x = (T)std::cos(angle);
-      twr[(size_t)k].y = (T)std::sin(angle);
-    }
-    e = hipMalloc((void **)&t.tw_half, twh.size() * sizeof(T2));
-    if (e == hipSuccess) e = hipMemcpy(t.tw_half, twh.data(), twh.size() * sizeof(T2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&t.twr, twr.size() * sizeof(T2));
-    if (e == hipSuccess) e = hipMemcpy(t.twr, twr.data(), twr.size() * sizeof(T2), hipMemcpyHostToDevice);
-    if (e == hipSuccess && log2n <= 14) {  // DCT twiddles W_4N^k, 0 <= k <= N/2, built in f64 and rounded once
-      std::vector<T2> tw4((size_t)(size / 2 + 1));
-      for (long long k = 0; k <= size / 2; ++k) {
-        const double angle = (-M_PI * (double)k) / (2.0 * (double)size);
-        tw4[(size_t)k].x = (T)std::cos(angle);
-        tw4[(size_t)k].y = (T)std::sin(angle);
-      }
-      e = hipMalloc((void **)&t.tw4n, tw4.size() * sizeof(T2));
-      if (e == hipSuccess) e = hipMemcpy(t.tw4n, tw4.data(), tw4.size() * sizeof(T2), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && log2n == 14 && !t.tw12) {
-      const std::vector<T2> t12 = build_twiddles<T2>(12);
-      e = hipMalloc((void **)&t.tw12, t12.size() * sizeof(T2));
-      if (e == hipSuccess) e = hipMemcpy(t.tw12, t12.data(), t12.size() * sizeof(T2), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && log2n >= 10 && log2n <= 13 && sizeof(T) == 4) {
-      // fused createWindow for spectrum_packed_kernel (N = 1024 ... 8192): sample n = (2 tid + e) + 2 TP q
-      const double f = 2.0 * M_PI / (double)(size - 1);
-      const int tp = (int)(size / 32);
-      std::vector<float> base((size_t)tp * 4), step(32);
-      for (int tdx = 0; tdx < tp; ++tdx)
-        for (int ee = 0; ee < 2; ++ee) {
-          base[4 * tdx + 2 * ee] = (float)std::cos(f * (2 * tdx + ee));
-          base[4 * tdx + 2 * ee + 1] = (float)std::sin(f * (2 * tdx + ee));
-        }
-      for (int q = 0; q < 16; ++q) {
-        step[2 * q] = (float)std::cos(f * 2.0 * tp * q);
-        step[2 * q + 1] = (float)std::sin(f * 2.0 * tp * q);
-      }
-      e = hipMalloc((void **)&t.wf_base, base.size() * sizeof(float));
-      if (e == hipSuccess) e = hipMemcpy(t.wf_base, base.data(), base.size() * sizeof(float), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMalloc((void **)&t.wf_step, step.size() * sizeof(float));
-      if (e == hipSuccess) e = hipMemcpy(t.wf_step, step.data(), step.size() * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && log2n == 14 && sizeof(T) == 4) {
-      // fused createWindow (fourier.ts:14-52: f = 2 pi i / (size - 1)): angle-addition tables, built in f64
-      const double f = 2.0 * M_PI / (double)(size - 1);
-      std::vector<float> base(256 * 4), step(64);
-      for (int tdx = 0; tdx < 256; ++tdx)
-        for (int ee = 0; ee < 2; ++ee) {
-          base[4 * tdx + 2 * ee] = (float)std::cos(f * (2 * tdx + ee));
-          base[4 * tdx + 2 * ee + 1] = (float)std::sin(f * (2 * tdx + ee));
-        }
-      for (int q = 0; q < 16; ++q) {
-        step[2 * q] = (float)std::cos(f * 512 * q);
-        step[2 * q + 1] = (float)std::sin(f * 512 * q);
-        step[32 + 2 * q] = (float)std::cos(f * (512 * q + 8192));
-        step[32 + 2 * q + 1] = (float)std::sin(f * (512 * q + 8192));
-      }
-      e = hipMalloc((void **)&t.wf_base, base.size() * sizeof(float));
-      if (e == hipSuccess) e = hipMemcpy(t.wf_base, base.data(), base.size() * sizeof(float), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMalloc((void **)&t.wf_step, step.size() * sizeof(float));
-      if (e == hipSuccess) e = hipMemcpy(t.wf_step, step.data(), step.size() * sizeof(float), hipMemcpyHostToDevice);
-    }
+  // radix table of the 4096-point sub-transforms: the split kernels on rows of 16384 and 8192 points, and the
+  // packed-real kernels at N = 16384
+  if ((full && (t.log2n2 == 14 || t.log2n2 == 13)) || (half && log2n == 14))
+    if (hipError_t e = upload_table(t, build_twiddles<T2>(12), &t.tw12)) return e;
+  if (!half) return hipSuccess;
+  if (hipError_t e = upload_packed_tables(t, log2n, size)) return e;
+  if constexpr (sizeof(T) == 4) {
+    if (log2n >= 10 && log2n <= 13) return upload_fused_window_tables(t, (int)(size / 32), size);  // spectrum_packed_kernel
+    if (log2n == 14) return upload_fused_window_tables(t, 256, size);
   }
-  return e;
+  return hipSuccess;
 }
 
 int require_device() {
@@ -948,24 +915,16 @@ int pdsp_max_size(int scalar_bytes) {  // incl. the four-step paths
   return 0;
 }
 
+// the development switches: each setter returns the previous value
 int pdsp_set_split16k(int enabled) {
-  const int prev = g_split16k;
-  g_split16k = enabled ? 1 : 0;
   g_split8k_f32 = (enabled & 2) ? 1 : 0;
-  return prev;
+  return std::exchange(g_split16k, enabled ? 1 : 0);
 }
-
-int pdsp_set_twopass(int enabled) {
-  const int prev = g_twopass;
-  g_twopass = enabled & 7;  // bit 0: tile passes; bit 1: their first form; bit 2 (or any value but 1): no fft_paired_kernel
-  return prev;
-}
-
-int pdsp_set_fused_window(int enabled) {
-  const int prev = g_fused_window;
-  g_fused_window = enabled ? 1 : 0;
-  return prev;
-}
+// bit 0: tile passes; bit 1: their first form; bit 2 (or any value but 1): no fft_paired_kernel
+int pdsp_set_twopass(int enabled) { return std::exchange(g_twopass, enabled & 7); }
+int pdsp_set_fused_window(int enabled) { return std::exchange(g_fused_window, enabled ? 1 : 0); }
+int pdsp_set_staged_small(int enabled) { return std::exchange(g_staged_small, enabled ? 1 : 0); }
+int pdsp_set_real_packed(int enabled) { return std::exchange(g_real_packed, enabled ? 1 : 0); }
 
 #define PDSP_DEFINE_PLAN_WINDOW(SUFFIX, T)                                                                  \
   int pdsp_plan_window_##SUFFIX(pdsp_plan *plan, int type, const T **window_out) {                          \
@@ -981,18 +940,6 @@ int pdsp_set_fused_window(int enabled) {
 PDSP_DEFINE_PLAN_WINDOW(f32, float)
 PDSP_DEFINE_PLAN_WINDOW(f64, double)
 #undef PDSP_DEFINE_PLAN_WINDOW
-
-int pdsp_set_staged_small(int enabled) {
-  const int prev = g_staged_small;
-  g_staged_small = enabled ? 1 : 0;
-  return prev;
-}
-
-int pdsp_set_real_packed(int enabled) {
-  const int prev = g_real_packed;
-  g_real_packed = enabled ? 1 : 0;
-  return prev;
-}
 
 int pdsp_set_host_precision(int bits) {
   const int prev = host_precision();
@@ -1464,13 +1411,56 @@ namespace pdsp_host {
 
 // The packed-real kernels (FIR filtering, the short-time pair, the DCT) run on the N/2-point tables, N = 64 ... 16384
 // in both precisions; the DCT also on W_4N^k.  `what` names the feature in the error text.
+int packed_size_error(const char *what, long long n) {
+  return fail(PDSP_ERR_UNSUPPORTED_SIZE, "%s needs a plan of 64 <= N <= 16384, got %lld", what, n);
+}
 template <typename T>
 int check_packed_plan(const pdsp_plan *plan, const char *what, bool need_tw4n) {
   if (!plan) return fail(PDSP_ERR_BAD_ARG, "plan is null");
   const Tables<T> &t = tables<T>(plan);
   if (plan->log2n < 6 || plan->log2n > pdsp::kMaxLog2N_f32 || !t.tw_half || !t.twr || (need_tw4n && !t.tw4n))
-    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "%s needs a plan of 64 <= N <= 16384, got %lld", what, plan->n);
+    return packed_size_error(what, plan->n);
   return PDSP_OK;
+}
+
+// The same gate for the bare size of a host form, behind the power-of-two check of the plan it will ask for.
+int check_packed_size(long long n, const char *what) {
+  if (!pdsp_is_pow2(n)) return fail(PDSP_ERR_SIZE_NOT_POW2, "FFT size must be power of two, got %lld", n);
+  if (n < 64 || n > 16384) return packed_size_error(what, n);
+  return PDSP_OK;
+}
+
+// Device memory of one host call, freed on every exit.
+struct DeviceBuf {
+  double *d = nullptr;
+  ~DeviceBuf() {
+    if (d) (void)hipFree(d);
+  }
+};
+
+// What the stream-ordered host forms of the packed features share, behind their own argument checks: the cached plan
+// of `n` points, pinned and locked for the call, with its device current; the plan's f64 window unless the type is
+// rect; one device buffer of `count` values.  enqueue(plan, stream, window, buffer) lays the buffer out, enqueues the
+// copies in and the call on the plan's stream; collect(buffer) copies the results out once that stream has drained.
+// (One explicit stream for every step: the two-pass ISTFT draws its scratch stream-ordered, StreamScratch.)
+template <class Enqueue, class Collect>
+int packed_host_call(long long n, int window_type, size_t count, Enqueue enqueue, Collect collect) {
+  if (int rc = require_device()) return rc;
+  CachedPlan cp;
+  if (int rc = cached_plan(n, &cp)) return rc;
+  pdsp_plan *const plan = cp.plan;
+  std::lock_guard<std::mutex> lk(plan->mu);
+  DeviceGuard g(plan->device);
+  PDSP_HIP_TRY(g.err);
+  const double *win = nullptr;
+  if (window_type != PDSP_WIN_RECT)
+    if (int rc = plan_window<double>(plan, window_type, &win)) return rc;
+  if (int rc = ensure_plan_stream(plan)) return rc;
+  DeviceBuf buf;
+  PDSP_HIP_TRY(hipMalloc((void **)&buf.d, count * sizeof(double)));
+  if (int rc = enqueue(plan, plan->stream, win, buf.d)) return rc;
+  PDSP_HIP_TRY(hipStreamSynchronize(plan->stream));
+  return collect(buf.d);
 }
 
 // Filters have at most N/2 taps (the tap count is checked ahead of the plan's size, behind its null check).
@@ -1606,12 +1596,7 @@ int pdsp_fir_filter_host_f64(const double *x, long long batch, long long len, co
   CachedPlan cp;
   if (int rc = cached_plan(fir_block_for(ntaps), &cp)) return rc;
   const long long bins = cp.plan->n / 2 + 1;
-  struct DeviceBuf {
-    double *d = nullptr;
-    ~DeviceBuf() {
-      if (d) (void)hipFree(d);
-    }
-  } sc;
+  DeviceBuf sc;
   const size_t nx = (size_t)xs, ny = (size_t)ys, nh = (size_t)(2 * bins);
   PDSP_HIP_TRY(hipMalloc((void **)&sc.d, (nx + ny + nh + (size_t)ntaps) * sizeof(double)));
   double *dx = sc.d, *dy = sc.d + nx, *dh = sc.d + nx + ny, *dt = dh + nh;
@@ -1677,21 +1662,12 @@ int istft_t(const pdsp_plan *plan, long long frames, const T *re_in, const T *im
 // Host forms: size, range and window type in the order of the device forms; the plan and its window come from the
 // host entry points' plan cache.
 int stft_host_checks(long long fft_size, long long hop, int window_type) {
-  if (!pdsp_is_pow2(fft_size)) return fail(PDSP_ERR_SIZE_NOT_POW2, "FFT size must be power of two, got %lld", fft_size);
-  if (fft_size < 64 || fft_size > 16384)
-    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "STFT needs a plan of 64 <= N <= 16384, got %lld", fft_size);
+  if (int rc = check_packed_size(fft_size, "STFT")) return rc;
   if (hop < 1) return fail(PDSP_ERR_BAD_ARG, "hop must be >= 1, got %lld", hop);
   if (window_type < PDSP_WIN_RECT || window_type > PDSP_WIN_BLACKMAN)
     return fail(PDSP_ERR_WINDOW_TYPE, "Unsupported window type: %d", window_type);
   return PDSP_OK;
 }
-
-struct HostDeviceBuf {
-  double *d = nullptr;
-  ~HostDeviceBuf() {
-    if (d) (void)hipFree(d);
-  }
-};
 
 }  // namespace pdsp_host
 
@@ -1713,11 +1689,7 @@ int pdsp_istft_f64(const pdsp_plan *plan, long long frames, const double *re_in,
   return istft_t<double>(plan, frames, re_in, im_in, hop, window, out, (hipStream_t)stream);
 }
 
-int pdsp_set_istft_chunk_frames(int frames) {
-  const int prev = g_istft_chunk_frames;
-  g_istft_chunk_frames = frames > 0 ? frames : 0;
-  return prev;
-}
+int pdsp_set_istft_chunk_frames(int frames) { return std::exchange(g_istft_chunk_frames, frames > 0 ? frames : 0); }
 
 int pdsp_stft_host_f64(const double *signal, long long len, long long fft_size, long long hop, int window_type,
                        double *re_out, double *im_out) {
@@ -1727,28 +1699,18 @@ int pdsp_stft_host_f64(const double *signal, long long len, long long fft_size, 
   const long long frames = 1 + (len - fft_size) / hop, bins = fft_size / 2 + 1;
   if (frames > 0x7fffffffLL || len > (1LL << 40)) return fail(PDSP_ERR_BAD_ARG, "signal too long: %lld samples", len);
   if (!signal || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
-  if (int rc = require_device()) return rc;
-  CachedPlan cp;
-  if (int rc = cached_plan(fft_size, &cp)) return rc;
-  pdsp_plan *const plan = cp.plan;
-  std::lock_guard<std::mutex> lk(plan->mu);
-  DeviceGuard g(plan->device);
-  PDSP_HIP_TRY(g.err);
-  const double *win = nullptr;
-  if (window_type != PDSP_WIN_RECT)
-    if (int rc = plan_window<double>(plan, window_type, &win)) return rc;
-  if (!plan->stream) PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
-  const hipStream_t s = plan->stream;
-  const size_t nx = (size_t)len, ny = (size_t)(frames * bins);
-  HostDeviceBuf sc;
-  PDSP_HIP_TRY(hipMalloc((void **)&sc.d, (nx + 2 * ny) * sizeof(double)));
-  double *dx = sc.d, *dre = sc.d + nx, *dim = dre + ny;
-  PDSP_HIP_TRY(hipMemcpyAsync(dx, signal, nx * sizeof(double), hipMemcpyHostToDevice, s));
-  if (int rc = stft_complex_t<double>(plan, frames, dx, fft_size, hop, win, dre, dim, s)) return rc;
-  PDSP_HIP_TRY(hipStreamSynchronize(s));
-  PDSP_HIP_TRY(hipMemcpy(re_out, dre, ny * sizeof(double), hipMemcpyDeviceToHost));
-  PDSP_HIP_TRY(hipMemcpy(im_out, dim, ny * sizeof(double), hipMemcpyDeviceToHost));
-  return PDSP_OK;
+  const size_t nx = (size_t)len, ny = (size_t)(frames * bins);  // buffer: signal | re | im
+  return packed_host_call(
+      fft_size, window_type, nx + 2 * ny,
+      [&](pdsp_plan *plan, hipStream_t s, const double *win, double *d) -> int {
+        PDSP_HIP_TRY(hipMemcpyAsync(d, signal, nx * sizeof(double), hipMemcpyHostToDevice, s));
+        return stft_complex_t<double>(plan, frames, d, fft_size, hop, win, d + nx, d + nx + ny, s);
+      },
+      [&](const double *d) -> int {
+        PDSP_HIP_TRY(hipMemcpy(re_out, d + nx, ny * sizeof(double), hipMemcpyDeviceToHost));
+        PDSP_HIP_TRY(hipMemcpy(im_out, d + nx + ny, ny * sizeof(double), hipMemcpyDeviceToHost));
+        return PDSP_OK;
+      });
 }
 
 int pdsp_istft_host_f64(const double *re, const double *im, long long frames, long long fft_size, long long hop,
@@ -1761,30 +1723,18 @@ int pdsp_istft_host_f64(const double *re, const double *im, long long frames, lo
       total > (1LL << 40) || in_count > (1LL << 40))
     return fail(PDSP_ERR_BAD_ARG, "frames %lld x hop %lld overflows", frames, hop);
   if (!re || !im || !out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
-  if (int rc = require_device()) return rc;
-  CachedPlan cp;
-  if (int rc = cached_plan(fft_size, &cp)) return rc;
-  pdsp_plan *const plan = cp.plan;
-  std::lock_guard<std::mutex> lk(plan->mu);
-  DeviceGuard g(plan->device);
-  PDSP_HIP_TRY(g.err);
-  const double *win = nullptr;
-  if (window_type != PDSP_WIN_RECT)
-    if (int rc = plan_window<double>(plan, window_type, &win)) return rc;
-  // the plan's own stream, synchronised before the results are copied out: the two-pass inverse draws its scratch
-  // stream-ordered (StreamScratch), so every step of the call is ordered on one explicit stream
-  if (!plan->stream) PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
-  const hipStream_t s = plan->stream;
-  const size_t nin = (size_t)in_count, ny = (size_t)total;
-  HostDeviceBuf sc;
-  PDSP_HIP_TRY(hipMalloc((void **)&sc.d, (2 * nin + ny) * sizeof(double)));
-  double *dre = sc.d, *dim = sc.d + nin, *dy = dim + nin;
-  PDSP_HIP_TRY(hipMemcpyAsync(dre, re, nin * sizeof(double), hipMemcpyHostToDevice, s));
-  PDSP_HIP_TRY(hipMemcpyAsync(dim, im, nin * sizeof(double), hipMemcpyHostToDevice, s));
-  if (int rc = istft_t<double>(plan, frames, dre, dim, hop, win, dy, s)) return rc;
-  PDSP_HIP_TRY(hipStreamSynchronize(s));
-  PDSP_HIP_TRY(hipMemcpy(out, dy, ny * sizeof(double), hipMemcpyDeviceToHost));
-  return PDSP_OK;
+  const size_t nin = (size_t)in_count, ny = (size_t)total;  // buffer: re | im | signal
+  return packed_host_call(
+      fft_size, window_type, 2 * nin + ny,
+      [&](pdsp_plan *plan, hipStream_t s, const double *win, double *d) -> int {
+        PDSP_HIP_TRY(hipMemcpyAsync(d, re, nin * sizeof(double), hipMemcpyHostToDevice, s));
+        PDSP_HIP_TRY(hipMemcpyAsync(d + nin, im, nin * sizeof(double), hipMemcpyHostToDevice, s));
+        return istft_t<double>(plan, frames, d, d + nin, hop, win, d + 2 * nin, s);
+      },
+      [&](const double *d) -> int {
+        PDSP_HIP_TRY(hipMemcpy(out, d + 2 * nin, ny * sizeof(double), hipMemcpyDeviceToHost));
+        return PDSP_OK;
+      });
 }
 
 /* ---- discrete cosine transform, types 2 and 3 ------------------------------ */
@@ -1851,31 +1801,24 @@ int pdsp_dct_f64(const pdsp_plan *plan, long long batch, const double *x, long l
 }
 
 int pdsp_dct_host_f64(const double *x, long long batch, long long n, int type, int norm, double *y) {
-  if (!pdsp_is_pow2(n)) return fail(PDSP_ERR_SIZE_NOT_POW2, "FFT size must be power of two, got %lld", n);
-  if (n < 64 || n > 16384) return fail(PDSP_ERR_UNSUPPORTED_SIZE, "DCT needs a plan of 64 <= N <= 16384, got %lld", n);
+  if (int rc = check_packed_size(n, "DCT")) return rc;
   if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
   if (int rc = check_dct_type_norm(type, norm)) return rc;
   long long count = 0;
   if (batch > 0x7fffffffLL || !mad_ok(batch, n, 0, &count) || count > (1LL << 40))
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x %lld overflows", batch, n);
   if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
-  if (int rc = require_device()) return rc;
-  CachedPlan cp;
-  if (int rc = cached_plan(n, &cp)) return rc;
-  pdsp_plan *const plan = cp.plan;
-  std::lock_guard<std::mutex> lk(plan->mu);
-  DeviceGuard g(plan->device);
-  PDSP_HIP_TRY(g.err);
-  if (!plan->stream) PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
-  const hipStream_t s = plan->stream;
   const size_t nx = (size_t)count;
-  HostDeviceBuf sc;
-  PDSP_HIP_TRY(hipMalloc((void **)&sc.d, nx * sizeof(double)));
-  PDSP_HIP_TRY(hipMemcpyAsync(sc.d, x, nx * sizeof(double), hipMemcpyHostToDevice, s));
-  if (int rc = dct_t<double>(plan, batch, sc.d, n, type, norm, sc.d, n, s)) return rc;  // in place
-  PDSP_HIP_TRY(hipStreamSynchronize(s));
-  PDSP_HIP_TRY(hipMemcpy(y, sc.d, nx * sizeof(double), hipMemcpyDeviceToHost));
-  return PDSP_OK;
+  return packed_host_call(
+      n, PDSP_WIN_RECT, nx,
+      [&](pdsp_plan *plan, hipStream_t s, const double *, double *d) -> int {
+        PDSP_HIP_TRY(hipMemcpyAsync(d, x, nx * sizeof(double), hipMemcpyHostToDevice, s));
+        return dct_t<double>(plan, batch, d, n, type, norm, d, n, s);  // in place
+      },
+      [&](const double *d) -> int {
+        PDSP_HIP_TRY(hipMemcpy(y, d, nx * sizeof(double), hipMemcpyDeviceToHost));
+        return PDSP_OK;
+      });
 }
 
 /* ---- Hilbert transform, analytic signal, envelope and phase ---------------- */
@@ -1932,9 +1875,7 @@ int pdsp_hilbert_f64(const pdsp_plan *plan, long long batch, const double *x, lo
 }
 
 int pdsp_hilbert_host_f64(const double *x, long long batch, long long len, long long n, int out_mode, double *y) {
-  if (!pdsp_is_pow2(n)) return fail(PDSP_ERR_SIZE_NOT_POW2, "FFT size must be power of two, got %lld", n);
-  if (n < 64 || n > 16384)
-    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "the Hilbert transform needs a plan of 64 <= N <= 16384, got %lld", n);
+  if (int rc = check_packed_size(n, "the Hilbert transform")) return rc;
   if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
   if (len < 1 || len > n) return fail(PDSP_ERR_BAD_ARG, "len must be 1 ... N = %lld, got %lld", n, len);
   if (int rc = check_hilbert_mode(out_mode)) return rc;
@@ -1943,24 +1884,17 @@ int pdsp_hilbert_host_f64(const double *x, long long batch, long long len, long 
   if (batch > 0x7fffffffLL || !mad_ok(batch, len, 0, &xcount) || !mad_ok(batch, yn, 0, &ycount) || ycount > (1LL << 40))
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x %lld overflows", batch, n);
   if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
-  if (int rc = require_device()) return rc;
-  CachedPlan cp;
-  if (int rc = cached_plan(n, &cp)) return rc;
-  pdsp_plan *const plan = cp.plan;
-  std::lock_guard<std::mutex> lk(plan->mu);
-  DeviceGuard g(plan->device);
-  PDSP_HIP_TRY(g.err);
-  if (!plan->stream) PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
-  const hipStream_t s = plan->stream;
-  // rows of n values on the device whatever len is (the wide path's layout), x behind y
+  // buffer: y | x, rows of n values on the device whatever len is (the wide path's layout)
   const size_t ny = (size_t)ycount, nx = (size_t)(batch * n);
-  HostDeviceBuf sc;
-  PDSP_HIP_TRY(hipMalloc((void **)&sc.d, (ny + nx) * sizeof(double)));
-  double *const dy = sc.d, *const dx = sc.d + ny;
-  PDSP_HIP_TRY(hipMemcpy2DAsync(dx, (size_t)n * sizeof(double), x, (size_t)len * sizeof(double),
-                                (size_t)len * sizeof(double), (size_t)batch, hipMemcpyHostToDevice, s));
-  if (int rc = hilbert_t<double>(plan, batch, dx, n, len, out_mode, dy, yn, s)) return rc;
-  PDSP_HIP_TRY(hipStreamSynchronize(s));
-  PDSP_HIP_TRY(hipMemcpy(y, dy, ny * sizeof(double), hipMemcpyDeviceToHost));
-  return PDSP_OK;
+  return packed_host_call(
+      n, PDSP_WIN_RECT, ny + nx,
+      [&](pdsp_plan *plan, hipStream_t s, const double *, double *d) -> int {
+        PDSP_HIP_TRY(hipMemcpy2DAsync(d + ny, (size_t)n * sizeof(double), x, (size_t)len * sizeof(double),
+                                      (size_t)len * sizeof(double), (size_t)batch, hipMemcpyHostToDevice, s));
+        return hilbert_t<double>(plan, batch, d + ny, n, len, out_mode, d, yn, s);
+      },
+      [&](const double *d) -> int {
+        PDSP_HIP_TRY(hipMemcpy(y, d, ny * sizeof(double), hipMemcpyDeviceToHost));
+        return PDSP_OK;
+      });
 }

@@ -23,6 +23,7 @@
 #include <mutex>
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/pdsp_hip.h"
 #include "../../include/pdsp_hip_dev.h"
@@ -140,47 +141,14 @@ struct Tables {
   int hp_np = 0;
   int hp_l[3] = {0, 0, 0};
   T2 *hp_tw[3] = {nullptr, nullptr, nullptr};
-  float *hp_win = nullptr;  // angle-addition tables of the fused cosine-sum windows (TileGeom::wa ...): wa | wb | wstep | we
+  float *hp_win = nullptr;  // angle-addition tables of the fused cosine-sum windows (TileGeom::wa ...): wa | wb | wstep | we | wq
   size_t hp_win_a = 0;      // entries (cos, sin pairs) of wa
+  // every device allocation made for this precision, the lazily built win[] entries included (upload_table in
+  // pdsp_capi.hip is the one place that adds to it).  Touched under plan->mu or before the plan is published only.
+  std::vector<void *> owned;
   void release() {
-    if (tw12) (void)hipFree(tw12);
-    tw12 = nullptr;
-    if (wf_base) (void)hipFree(wf_base);
-    if (wf_step) (void)hipFree(wf_step);
-    wf_base = wf_step = nullptr;
-    if (tws4) (void)hipFree(tws4);
-    tws4 = nullptr;
-    if (tws2) (void)hipFree(tws2);
-    tws2 = nullptr;
-
-    if (tw8) (void)hipFree(tw8);
-    tw8 = nullptr;
-    for (T2 *&q : tp_tw) {
-      if (q) (void)hipFree(q);
-      q = nullptr;
-    }
-    tp_np = 0;
-    for (T2 *&q : hp_tw) {
-      if (q) (void)hipFree(q);
-      q = nullptr;
-    }
-    hp_np = 0;
-    if (hp_win) (void)hipFree(hp_win);
-    hp_win = nullptr;
-    if (twa) (void)hipFree(twa);
-    if (twb) (void)hipFree(twb);
-    if (tw1) (void)hipFree(tw1);
-    twa = twb = tw1 = nullptr;
-    if (tw) (void)hipFree(tw);
-    if (tw_half) (void)hipFree(tw_half);
-    if (twr) (void)hipFree(twr);
-    if (tw4n) (void)hipFree(tw4n);
-    tw4n = nullptr;
-    for (T *&w : win) {
-      if (w) (void)hipFree(w);
-      w = nullptr;
-    }
-    tw = tw_half = twr = nullptr;
+    for (void *p : owned) (void)hipFree(p);
+    *this = Tables{};
   }
 };
 
