@@ -509,6 +509,60 @@ PDSP_API int pdsp_hilbert_f64(const pdsp_plan *plan, long long batch, const doub
 PDSP_API int pdsp_hilbert_host_f64(const double *x, long long batch, long long len, long long n, int out_mode,
                                    double *y);
 
+/* ---- polyphase rate change: upfirdn / resample_poly, f32 / f64 -------------------------------- */
+/* The reference's roadmap, "Filters and utilities": "resampling to a uniform grid", with its "windowed-sinc filter
+ * design helpers".  Conventions are scipy.signal.upfirdn's and scipy.signal.resample_poly's (padtype "constant").
+ * The primitive, for real rows x[0..len), real taps h[0..ntaps) and integers up, down >= 1, t0 >= 0:
+ *   y[m] = sum_k h[m down + t0 - k up] x[k],   0 <= k < len, 0 <= tap index < ntaps,   m = 0 ... y_len - 1
+ * -- upsample by `up` with zeros, filter, keep every `down`-th sample from t0 on -- computed in the time domain by one
+ * launch that neither stores the stuffed zeros nor computes a discarded output.
+ *   scipy.signal.upfirdn(h, x, up, down):   t0 = 0, y_len = ((len - 1) up + ntaps - 1) / down + 1; up, down as given.
+ *   scipy.signal.resample_poly(x, up, down, window): up, down divided by their gcd, the taps times up,
+ *     t0 = (ntaps - 1) / 2, y_len = ceil(len up / down); the default taps are
+ *     scipy.signal.firwin(2 half + 1, 1 / max(up, down), window=("kaiser", 5.0)), half = 10 max(up, down); a window
+ *     given as an array is the taps; up == down after the reduction is the identity (one tap, 1: y == x bit for bit).
+ * Every output is summed over its taps in ascending order, one fma per term, so a sample's value depends on neither
+ * the batch, the row's placement nor where tiles meet.  f32 ~6e-8 * T * sum|h||x| per output, T = ceil(ntaps / up)
+ * (a bound, (T + 2) eps against an f64 reference); f64 the same with 2^-52.
+ * Supported: 1 <= up, down <= 8192, 1 <= ntaps <= 8192 (beyond: PDSP_ERR_UNSUPPORTED_SIZE; so is a default filter of
+ * more than 8192 taps, max(up, down) > 409 after the reduction), 0 <= t0 < ntaps + up, len >= 1, any y_len >= 0
+ * (outputs past the data are 0), rows at strides >= their lengths.  Every argument is checked before any device work:
+ * a null handle or buffer, up / down / ntaps / len < 1, a negative batch or y_len, short strides and extents that
+ * overflow give PDSP_ERR_BAD_ARG, and so does a y whose byte extent ((batch - 1) * y_stride + y_len elements) meets
+ * that of x. */
+typedef struct pdsp_resampler pdsp_resampler;
+/* The primitive: the taps as given (copied), up and down not reduced.  A resampler is tied to no FFT size; it holds
+ * its taps as a phase-major table in f64, rounded once per precision and uploaded to `device` (< 0: the device
+ * current at the first call) on first use.  Creation itself touches no device. */
+PDSP_API int pdsp_resampler_create(int device, long long up, long long down, const double *taps, long long ntaps,
+                                   long long t0, pdsp_resampler **out);
+/* scipy.signal.resample_poly's set-up: the reduction by the gcd, the taps (NULL: the default design) times up, t0. */
+PDSP_API int pdsp_resampler_create_poly(int device, long long up, long long down, const double *taps_or_null,
+                                        long long ntaps, pdsp_resampler **out);
+PDSP_API int pdsp_resampler_destroy(pdsp_resampler *rs);
+/* after the reduction; the taps as convolved (resample_poly: times up), pdsp_resampler_ntaps values */
+PDSP_API long long pdsp_resampler_up(const pdsp_resampler *rs);
+PDSP_API long long pdsp_resampler_down(const pdsp_resampler *rs);
+PDSP_API long long pdsp_resampler_ntaps(const pdsp_resampler *rs);
+PDSP_API long long pdsp_resampler_t0(const pdsp_resampler *rs);
+PDSP_API int pdsp_resampler_taps(const pdsp_resampler *rs, double *taps);
+/* full != 0: upfirdn's ((len - 1) up + ntaps - 1) / down + 1; else resample_poly's ceil(len up / down) */
+PDSP_API int pdsp_resample_output_len(const pdsp_resampler *rs, long long len, int full, long long *y_len);
+/* `batch` rows of `len` samples at x_stride -> rows of y_len outputs at y_stride (device pointers, any alignment) */
+PDSP_API int pdsp_upfirdn_f32(const pdsp_resampler *rs, long long batch, const float *x, long long len,
+                              long long x_stride, float *y, long long y_len, long long y_stride, pdsp_stream stream);
+PDSP_API int pdsp_upfirdn_f64(const pdsp_resampler *rs, long long batch, const double *x, long long len,
+                              long long x_stride, double *y, long long y_len, long long y_stride, pdsp_stream stream);
+/* The default filter of resample_poly for up / down (reduced by their gcd first), times up: host only, no device.
+ * *ntaps receives the count, 20 max(up, down) + 1 (1 when up == down); taps may be NULL to ask for the count alone. */
+PDSP_API int pdsp_resample_design_f64(long long up, long long down, double *taps, long long *ntaps);
+/* Host f64 drop-in forms (synchronous, f64 arithmetic): `batch` contiguous rows of len >= 1 samples in, contiguous
+ * rows of ceil(len up / down) (resample_poly) or ((len - 1) up + ntaps - 1) / down + 1 (upfirdn) outputs. */
+PDSP_API int pdsp_resample_poly_host_f64(const double *x, long long batch, long long len, long long up,
+                                         long long down, const double *taps_or_null, long long ntaps, double *y);
+PDSP_API int pdsp_upfirdn_host_f64(const double *h, long long ntaps, const double *x, long long batch, long long len,
+                                   long long up, long long down, double *y);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,15 @@ from .spectrum import SpectrumPeak, SpectrumResult, spectrum, spectrumBatch  # n
 from .stft import istft, stft  # noqa: F401
 from .dct import dct, idct  # noqa: F401
 from .hilbert import envelope, hilbert, instantaneous_phase  # noqa: F401
+from .resample import (  # noqa: F401
+    Resampler,
+    Upfirdn,
+    design_taps,
+    resample_poly,
+    resamplePoly,
+    upfirdn,
+    upfirdnHost,
+)
 
 __all__ = [
     "ComplexArray", "Radix2Fft", "createComplexArray", "isPowerOfTwo", "nextPowerOfTwo",
@@ -30,4 +39,5 @@ __all__ = [
     "magnitude", "phase", "spectrum", "spectrumBatch", "SpectrumPeak", "SpectrumResult", "PdspError",
     "FirFilter", "fir_filter", "firFilter", "stft", "istft", "dct", "idct",
     "hilbert", "envelope", "instantaneous_phase",
+    "Resampler", "Upfirdn", "resample_poly", "upfirdn", "resamplePoly", "upfirdnHost", "design_taps",
 ]

@@ -142,6 +142,20 @@ def _load() -> C.CDLL:
         "pdsp_hilbert_f32": ([vp, ll, vp, ll, ll, i32, vp, ll, vp], i32),
         "pdsp_hilbert_f64": ([vp, ll, vp, ll, ll, i32, vp, ll, vp], i32),
         "pdsp_hilbert_host_f64": ([dp, ll, ll, ll, i32, dp], i32),
+        "pdsp_resampler_create": ([i32, ll, ll, dp, ll, ll, C.POINTER(vp)], i32),
+        "pdsp_resampler_create_poly": ([i32, ll, ll, dp, ll, C.POINTER(vp)], i32),
+        "pdsp_resampler_destroy": ([vp], i32),
+        "pdsp_resampler_up": ([vp], ll),
+        "pdsp_resampler_down": ([vp], ll),
+        "pdsp_resampler_ntaps": ([vp], ll),
+        "pdsp_resampler_t0": ([vp], ll),
+        "pdsp_resampler_taps": ([vp, dp], i32),
+        "pdsp_resample_output_len": ([vp, ll, i32, C.POINTER(ll)], i32),
+        "pdsp_upfirdn_f32": ([vp, ll, vp, ll, ll, vp, ll, ll, vp], i32),
+        "pdsp_upfirdn_f64": ([vp, ll, vp, ll, ll, vp, ll, ll, vp], i32),
+        "pdsp_resample_design_f64": ([ll, ll, dp, C.POINTER(ll)], i32),
+        "pdsp_resample_poly_host_f64": ([dp, ll, ll, ll, ll, dp, ll, dp], i32),
+        "pdsp_upfirdn_host_f64": ([dp, ll, dp, ll, ll, ll, ll, dp], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -1,6 +1,6 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from eight translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from nine translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
@@ -11,6 +11,7 @@
 //   pdsp_kernels_stft.hip         complex STFT and its overlap-add inverse, f32 and f64
 //   pdsp_kernels_dct.hip          DCT-II and DCT-III, f32 and f64
 //   pdsp_kernels_hilbert.hip      Hilbert transform, analytic signal, envelope and phase, f32 and f64
+//   pdsp_kernels_resample.hip     polyphase rate change (upfirdn / resample_poly), f32 and f64
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -291,5 +292,23 @@ int hilbert_dev(const pdsp_plan *plan, long long batch, const T *x, long long x_
 // (ANALYTIC: to 16 bytes) with a stride that keeps that
 bool hilbert_fast_path(const void *x, long long x_stride, long long len, long long n, int out_mode, const void *y,
                        long long y_stride, size_t elem);
+
+// pdsp_upfirdn_* after validation (pdsp_kernels_resample.hip): 1 <= up, down, ntaps <= 8192, 0 <= t0 < ntaps + up,
+// len, batch, y_len >= 1, strides >= the row lengths, y_len * down + t0 within 64 bits, no overlap.  g: the phase-major
+// tap table, up * ceil(ntaps / up) device values.
+template <typename T>
+int upfirdn_dev(const T *g, long long up, long long down, long long ntaps, long long t0, long long batch, const T *x,
+                long long len, long long x_stride, T *y, long long y_len, long long y_stride, hipStream_t s);
+// The tile of one launch (the rule: pdsp_kernels_resample.hip): the instantiation (r outputs per item,
+// win: sliding window, gt: taps in global memory), taps per phase and their LDS row stride, outputs per phase and
+// tile, samples staged, dynamic LDS, items per tile.  false: nothing fits (not within the supported domain).
+struct UpfirdnTile {
+  int r = 0;
+  bool win = false, gt = false;
+  int tn = 0, tp = 0, bper = 0, span = 0;
+  size_t lds_bytes = 0;
+  long long items = 0;
+};
+bool upfirdn_tile(long long up, long long down, long long ntaps, long long y_len, size_t elem, UpfirdnTile *out);
 
 }  // namespace pdsp_host

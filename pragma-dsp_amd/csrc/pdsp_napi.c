@@ -564,6 +564,68 @@ static napi_value FirFilter(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* resamplePoly(signal, up, down, taps, out): taps of length 0 = the default design; out holds ceil(len up / down)
+ * outputs.  upfirdn(h, signal, up, down, out): out holds ((len - 1) up + ntaps - 1) / down + 1.  Arguments the library
+ * refuses reach it unchanged (it fails before touching the output), so its message is what the caller sees.
+ * [ROADMAP.md, "Filters and utilities"; include/pdsp_hip.h, "polyphase rate change"] */
+static napi_value ResamplePoly(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return NULL;
+  double *x, *h, *y;
+  size_t nx, nh, ny;
+  int64_t up, down;
+  if (!f64_array(env, argv[0], &x, &nx) || !get_i64(env, argv[1], &up) || !get_i64(env, argv[2], &down) ||
+      !f64_array(env, argv[3], &h, &nh) || !f64_array(env, argv[4], &y, &ny))
+    return NULL;
+  if (up >= 1 && up <= 8192 && down >= 1 && down <= 8192 && nx >= 1 &&
+      (long long)ny < ((long long)nx * up + down - 1) / down) {
+    napi_throw_error(env, NULL, "pdsp_napi: resamplePoly output too small");
+    return NULL;
+  }
+  if (pdsp_resample_poly_host_f64(x, 1, (long long)nx, up, down, nh ? h : NULL, (long long)nh, y) != PDSP_OK)
+    return throw_pdsp(env);
+  return NULL;
+}
+
+static napi_value Upfirdn(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return NULL;
+  double *x, *h, *y;
+  size_t nx, nh, ny;
+  int64_t up, down;
+  if (!f64_array(env, argv[0], &h, &nh) || !f64_array(env, argv[1], &x, &nx) || !get_i64(env, argv[2], &up) ||
+      !get_i64(env, argv[3], &down) || !f64_array(env, argv[4], &y, &ny))
+    return NULL;
+  if (up >= 1 && up <= 8192 && down >= 1 && down <= 8192 && nx >= 1 && nh >= 1 && nh <= 8192 &&
+      (long long)ny < (((long long)nx - 1) * up + (long long)nh - 1) / down + 1) {
+    napi_throw_error(env, NULL, "pdsp_napi: upfirdn output too small");
+    return NULL;
+  }
+  if (pdsp_upfirdn_host_f64(h, (long long)nh, x, 1, (long long)nx, up, down, y) != PDSP_OK) return throw_pdsp(env);
+  return NULL;
+}
+
+/* resampleDesign(up, down, out) -> the number of taps; out of length 0 asks for the count alone */
+static napi_value ResampleDesign(napi_env env, napi_callback_info info) {
+  napi_value argv[3], res;
+  if (!get_args(env, info, 3, argv)) return NULL;
+  double *h;
+  size_t nh;
+  int64_t up, down;
+  if (!get_i64(env, argv[0], &up) || !get_i64(env, argv[1], &down) || !f64_array(env, argv[2], &h, &nh)) return NULL;
+  long long n = 0;
+  if (pdsp_resample_design_f64(up, down, NULL, &n) != PDSP_OK) return throw_pdsp(env);
+  if (nh) {
+    if ((long long)nh < n) {
+      napi_throw_error(env, NULL, "pdsp_napi: resampleDesign output too small");
+      return NULL;
+    }
+    if (pdsp_resample_design_f64(up, down, h, &n) != PDSP_OK) return throw_pdsp(env);
+  }
+  NAPI_OK_OR_THROW(env, napi_create_int64(env, n, &res));
+  return res;
+}
+
 /* stft(signal, fftSize, hopSize, windowType, real, imag): real / imag receive F x (fftSize/2 + 1) bins,
  * F = 1 + (len - fftSize) / hopSize.  fftSize and hopSize are bounded before any multiply; arguments the library
  * refuses reach it unchanged (it fails before touching the outputs), so its message is what the caller sees. */
@@ -670,7 +732,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"spectrum", Spectrum},     {"binFrequencies", BinFrequencies}, {"fftShift", FftShift},
       {"spectrumBatch", SpectrumBatch}, {"spectrumRows", SpectrumRows},
       {"nextPow2", NextPow2},     {"deviceCount", DeviceCount},
-      {"firFilter", FirFilter},   {"stft", Stft},               {"istft", Istft},
+      {"firFilter", FirFilter},   {"resamplePoly", ResamplePoly}, {"upfirdn", Upfirdn},
+      {"resampleDesign", ResampleDesign},   {"stft", Stft},               {"istft", Istft},
       {"dct", Dct},                 {"hilbert", Hilbert},
   };
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {

@@ -2,6 +2,7 @@
 import * as coreNs from './core';
 import * as fourierNs from './fourier';
 import * as filtersNs from './filters';
+import * as resampleNs from './resample';
 import * as stftNs from './stft';
 import * as dctNs from './dct';
 import * as hilbertNs from './hilbert';
@@ -32,6 +33,9 @@ export const fourier: {
 };
 export const filters: {
   firFilter: typeof filtersNs.firFilter;
+  resamplePoly: typeof resampleNs.resamplePoly;
+  upfirdn: typeof resampleNs.upfirdn;
+  designResampleTaps: typeof resampleNs.designResampleTaps;
 };
 export const stft: {
   stft: typeof stftNs.stft;

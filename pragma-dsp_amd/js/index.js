@@ -14,6 +14,7 @@ const filters = require('./filters');
 const stft = require('./stft');
 const dct = require('./dct');
 const hilbert = require('./hilbert');
+const resample = require('./resample');
 
 module.exports = {
   spectrum: s.spectrum,
@@ -39,7 +40,12 @@ module.exports = {
 // pragma-dsp/filters: a module the reference only plans (ROADMAP.md, "Filters and utilities").  Reachable as
 // `.filters` but not enumerated, so that the key list of the reference's three surfaces stays exactly theirs.
 Object.defineProperty(module.exports, 'filters', {
-  value: { firFilter: filters.firFilter },
+  value: {
+    firFilter: filters.firFilter,
+    resamplePoly: resample.resamplePoly,
+    upfirdn: resample.upfirdn,
+    designResampleTaps: resample.designResampleTaps,
+  },
   enumerable: false,
 });
 // pragma-dsp/xform/stft: planned by the reference (ROADMAP.md, "A) STFT"), not enumerated for the same reason.
