@@ -54,6 +54,22 @@ PDSP_API int pdsp_set_real_packed(int enabled);
  * for every value; tests use small ones to run many chunks on small inputs.  Returns the previous value. */
 PDSP_API int pdsp_set_istft_chunk_frames(int frames);
 
+/* The tile of the polyphase rate change (pdsp_upfirdn_*), forced.  mode & 15 is the instantiation:
+ * 0 (default) = the tile rule, 1 = R = 4, 2 = R = 8 with the sliding window (WIN), 3 = R = 1, 4 = R = 1 with the taps
+ * read from global memory (GT).  mode >> 4 caps B, the outputs per phase and tile: 0 = no cap, n = at most n rounded
+ * up to a multiple of R (applied after the rule's own cap by the row's outputs; with instantiation 0 the rule then
+ * chooses among the capped tiles).  A forced instantiation is never replaced: where it is not legal for a call (WIN
+ * with down != 1) or has no tile within 160 KiB of LDS, the call fails with PDSP_ERR_UNSUPPORTED_SIZE before any
+ * launch.  Results are bit-identical for every value; tests use it to run each instantiation, and many small tiles,
+ * on small inputs.  A mode that is negative or names no instantiation leaves the setting as it is.  Returns the
+ * previous value. */
+PDSP_API int pdsp_set_upfirdn_tile(int mode);
+/* The tile a pdsp_upfirdn_* call with these arguments (elem_bytes 4 or 8) would launch under the current
+ * pdsp_set_upfirdn_tile: info = r, win, gt, tn, tp, bper, span, lds_bytes, items.  Needs no device.
+ * 1 <= up, down, ntaps <= 8192, y_len >= 1. */
+PDSP_API int pdsp_dev_upfirdn_tile(long long up, long long down, long long ntaps, long long y_len, int elem_bytes,
+                                   long long info[9]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,8 @@ def _load() -> C.CDLL:
         "pdsp_resample_design_f64": ([ll, ll, dp, C.POINTER(ll)], i32),
         "pdsp_resample_poly_host_f64": ([dp, ll, ll, ll, ll, dp, ll, dp], i32),
         "pdsp_upfirdn_host_f64": ([dp, ll, dp, ll, ll, ll, ll, dp], i32),
+        "pdsp_set_upfirdn_tile": ([i32], i32),
+        "pdsp_dev_upfirdn_tile": ([ll, ll, ll, ll, i32, C.POINTER(ll)], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -2159,6 +2159,26 @@ int pdsp_upfirdn_f64(const pdsp_resampler *rs, long long batch, const double *x,
   return upfirdn_t<double>(rs, batch, x, len, x_stride, y, y_len, y_stride, (hipStream_t)stream);
 }
 
+int pdsp_set_upfirdn_tile(int mode) {
+  const int prev = g_upfirdn_tile;
+  if (mode >= 0 && (mode & 15) <= 4) g_upfirdn_tile = mode;
+  return prev;
+}
+
+int pdsp_dev_upfirdn_tile(long long up, long long down, long long ntaps, long long y_len, int elem_bytes,
+                          long long info[9]) {
+  if (!info) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  if (int rc = check_resample_ratio(up, down)) return rc;
+  if (int rc = check_resample_ntaps(ntaps)) return rc;
+  if (y_len < 1) return fail(PDSP_ERR_BAD_ARG, "y_len must be >= 1, got %lld", y_len);
+  if (elem_bytes != 4 && elem_bytes != 8) return fail(PDSP_ERR_BAD_ARG, "elem_bytes must be 4 or 8, got %d", elem_bytes);
+  UpfirdnTile t;
+  if (int rc = upfirdn_tile_checked(up, down, ntaps, y_len, (size_t)elem_bytes, &t)) return rc;
+  const long long v[9] = {t.r, t.win, t.gt, t.tn, t.tp, t.bper, t.span, (long long)t.lds_bytes, t.items};
+  std::memcpy(info, v, sizeof(v));
+  return PDSP_OK;
+}
+
 int pdsp_resample_design_f64(long long up, long long down, double *taps, long long *ntaps) {
   if (!ntaps) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   std::vector<double> h;

@@ -310,5 +310,9 @@ struct UpfirdnTile {
   long long items = 0;
 };
 bool upfirdn_tile(long long up, long long down, long long ntaps, long long y_len, size_t elem, UpfirdnTile *out);
+// pdsp_set_upfirdn_tile: low 4 bits 0 = the rule, 1 ... 4 = one instantiation forced; the rest a cap on bper (0: none)
+extern int g_upfirdn_tile;
+// upfirdn_tile, or PDSP_ERR_UNSUPPORTED_SIZE with a message that names a forced instantiation
+int upfirdn_tile_checked(long long up, long long down, long long ntaps, long long y_len, size_t elem, UpfirdnTile *out);
 
 }  // namespace pdsp_host

@@ -26,7 +26,8 @@ def test_library_exports_every_declared_symbol(pdsp):
         assert hasattr(raw, s), f"{s} declared in include/*.h but not exported"
     # the boundary header carries no development switch: only the user-facing precision knob
     assert [s for s in syms if s.startswith("pdsp_set_")] == ["pdsp_set_host_precision"]
-    assert all(s.startswith("pdsp_set_") for s in dev) and not set(dev) & set(syms)
+    assert not [s for s in syms if s.startswith("pdsp_dev_")]
+    assert all(s.startswith(("pdsp_set_", "pdsp_dev_")) for s in dev) and not set(dev) & set(syms)
     # and the ctypes binding covers all of them
     assert set(syms) | set(dev) == set(pdsp.lib._pdsp_symbols)
     assert pdsp.lib.pdsp_version() >= 100

@@ -97,7 +97,10 @@ def test_user_taps(ntaps, up, dt):
 @pytest.mark.parametrize("dt", DTYPES, ids=["f32", "f64"])
 @pytest.mark.parametrize("up,down,n", [(3, 2, 300), (1, 1, 300), (5, 1, 1), (8191, 8192, 3), (4096, 8192, 9)])
 def test_upfirdn_full_output(up, down, n, dt):
-    h = user_taps(8192 if up > 100 else 17)  # the last two: the tap table leaves LDS no room for a span in f64
+    # the last two, 8192 taps: 8191/8192 reads its taps from global memory in f64 (no room for a span beside them) and
+    # runs plain R = 1 in f32; 4096/8192 runs R = 1 with the taps in LDS in both, in f64 at the unpadded stride
+    # tp == tn (tests/test_gpu_resample_paths.py asks the library which)
+    h = user_taps(8192 if up > 100 else 17)
     r = pd.Upfirdn(h, up, down, device="cuda:0", dtype=dt)
     y = check(r, signal((3, n), dt, up), dt, f"upfirdn {up}/{down}")
     assert y.shape[1] == ((n - 1) * up + h.size - 1) // down + 1

@@ -35,6 +35,25 @@ def resample_ref(x, up, down, h, t0, y_len, abs=False):  # noqa: A002
     return y
 
 
+def resample_ref_direct(x, up, down, h, t0, y_len, abs=False):  # noqa: A002
+    """The same sum in its gather form, for ratios at which the stuffed signal is out of reach (up = 8191):
+    y[m] = sum_{j < T} h[p + j up] x[k0 - j], q = m down + t0, p = q mod up, k0 = q div up, T = ceil(ntaps / up), in
+    f64, j ascending, all m at once.  Pinned to resample_ref below."""
+    x = np.atleast_2d(np.asarray(x, dtype=np.float64))
+    h = np.asarray(h, dtype=np.float64)
+    if abs:
+        x, h = np.abs(x), np.abs(h)
+    rows, n = x.shape
+    q = t0 + np.arange(y_len, dtype=np.int64) * down
+    p, k0 = q % up, q // up
+    y = np.zeros((rows, y_len))
+    for j in range(-(-h.size // up)):
+        tap, k = p + j * up, k0 - j
+        ok = (tap < h.size) & (k >= 0) & (k < n)
+        y[:, ok] += h[tap[ok]] * x[:, k[ok]]
+    return y
+
+
 def poly_setup(up, down, taps=None):
     """(up, down, h, t0) as scipy.signal.resample_poly sets them up; the default taps come from the library's design
     (pinned to scipy.signal.firwin below)."""
@@ -81,6 +100,28 @@ def test_reference_is_scipys_upfirdn(up, down, n, taps):
     got = resample_ref(x, up, down, h, 0, ((n - 1) * up + taps - 1) // down + 1)[0]
     assert got.shape == want.shape
     assert np.abs(got - want).max() <= 1e-13 * np.abs(want).max()
+
+
+@pytest.mark.parametrize("taps", [17, 16])
+@pytest.mark.parametrize("up,down,n", CASES)
+def test_direct_reference_is_the_stuffed_one(up, down, n, taps):
+    """Both are f64 sums of the same at most T non-zero terms, each off its exact value by at most T u A[m]:
+    |direct - stuffed| <= T 2^-52 A[m], and exactly 0 where no term exists."""
+    x = np.random.default_rng(up * 1000 + down + n).standard_normal((2, n))
+    h = user_taps(taps)
+    t = -(-taps // up)
+    for t0 in (0, 1, up, taps + up - 1):
+        natural = max(-(-((n - 1) * up + taps - t0) // down), 0)
+        for y_len in (max(natural // 2, 1), natural + 10):
+            want = resample_ref(x, up, down, h, t0, y_len)
+            a = resample_ref(x, up, down, h, t0, y_len, abs=True)
+            got = resample_ref_direct(x, up, down, h, t0, y_len)
+            assert got.shape == want.shape == (2, y_len)
+            assert np.all(np.abs(got - want) <= t * 2.0 ** -52 * a), (t0, y_len)
+            assert np.all(got[a == 0] == 0.0) and np.all(want[a == 0] == 0.0)
+            assert np.array_equal(resample_ref_direct(x, up, down, h, t0, y_len, abs=True) == 0, a == 0)
+            if y_len > natural:
+                assert np.all(got[:, natural:] == 0.0)
 
 
 @pytest.mark.parametrize("up,down", sorted({(u, d) for u, d, _ in CASES}))
