@@ -200,17 +200,26 @@ PDSP_API int pdsp_fft_inverse_f32(const pdsp_plan *plan, long long batch,
 
 /* ---- device-pointer elementwise helpers (f32) -------------------------- */
 
-/* applyWindow row by row, src/xform/fourier.ts:54-67: out[b][i] = in[b][i]*win[i]. */
+/* Aliasing, for every helper of this section and its f64 twin: an output may share bytes with an
+ * input of the same extent only where the two begin at the same address (each element is read
+ * before it is written); any other overlap is refused with PDSP_ERR_BAD_ARG, "output overlaps
+ * input", before anything is launched. */
+
+/* applyWindow row by row, src/xform/fourier.ts:54-67: out[b][i] = in[b][i]*win[i].  out == in is
+ * allowed; out partially overlapping in, or overlapping window, is refused, and so is a batch * n
+ * that overflows. */
 PDSP_API int pdsp_apply_window_f32(long long batch, long long n, const float *in,
                                    const float *window, float *out, pdsp_stream stream);
-/* magnitude, src/xform/fourier.ts:98-109 (sqrt(re^2+im^2) in f32; not the
- * overflow-safe hypot).  Within 1 ulp while re^2 + im^2 is a normal f32:
+/* magnitude, src/xform/fourier.ts:98-109 (sqrt(re^2+im^2), the sum of squares rounded
+ * to f32 once and its f32 sqrt; not the overflow-safe hypot, and a NaN operand gives NaN
+ * whatever the other is).  Within 1 ulp while re^2 + im^2 is a normal f32:
  * 1.1e-19 <= |X| <= 1.8e19.  The fused amplitude stores of pdsp_spectrum_f32 /
  * pdsp_spectrum_peaks_f32 square either the bin or half its scaled amplitude, so
  * their rows hold for |X_k| <= 1.8e19 and amplitudes >= 2.2e-19; see DESIGN.md §1. */
 PDSP_API int pdsp_magnitude_f32(long long count, const float *re, const float *im,
                                 float *out, pdsp_stream stream);
-/* phase, src/xform/fourier.ts:111-120: atan2(im, re). */
+/* phase, src/xform/fourier.ts:111-120: atan2(im, re).  For magnitude and phase alike, out == re
+ * or out == im is allowed; out partially overlapping either is refused. */
 PDSP_API int pdsp_phase_f32(long long count, const float *re, const float *im,
                             float *out, pdsp_stream stream);
 
@@ -222,7 +231,11 @@ PDSP_API int pdsp_phase_f32(long long count, const float *re, const float *im,
  * for SCALE (real s_re) and MUL_SCALAR; out = conj(a) for CONJ.  divScalar is MUL_SCALAR by the
  * host-computed reciprocal, as complex.ts:176-186 does.  out may alias a, and b may alias out when
  * b_len == count (every element is read before it is written); a broadcast b (b_len < count) must
- * not overlap out. */
+ * not overlap out.  Enforced plane by plane: an out plane may share bytes with a_re, a_im, or with
+ * b_re / b_im when b_len == count, only where the two planes begin at the same address (exact in
+ * place, a == b == out, and out_re == a_im with out_im == a_re are all allowed); out_re and out_im
+ * must not overlap each other; a broadcast b must share no byte with either out plane.  Anything
+ * else is refused with PDSP_ERR_BAD_ARG, "output overlaps input".  b is ignored by the unary ops. */
 typedef enum pdsp_complex_op {
   PDSP_CX_ADD = 0, PDSP_CX_SUB = 1, PDSP_CX_MUL = 2, PDSP_CX_DIV = 3,
   PDSP_CX_CONJ = 4, PDSP_CX_SCALE = 5, PDSP_CX_MUL_SCALAR = 6

@@ -70,6 +70,14 @@ PDSP_API int pdsp_set_upfirdn_tile(int mode);
 PDSP_API int pdsp_dev_upfirdn_tile(long long up, long long down, long long ntaps, long long y_len, int elem_bytes,
                                    long long info[9]);
 
+/* Which complex_op_kernel instantiation a pdsp_complex_op_f32 call with these arguments launches: *vec4 = 1 for
+ * four values per thread in 16-byte accesses (a_re, a_im, out_re, out_im, and for a binary op b_re, b_im, all on
+ * 16-byte boundaries; count, and for a binary op b_len, multiples of 4), 0 for one value per thread.  The pointers
+ * are only looked at.  Needs no device. */
+PDSP_API int pdsp_dev_complex_op_vec4(int op, long long count, const float *a_re, const float *a_im,
+                                      const float *b_re, const float *b_im, long long b_len, const float *out_re,
+                                      const float *out_im, int *vec4);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,7 @@ def _load() -> C.CDLL:
         "pdsp_upfirdn_host_f64": ([dp, ll, dp, ll, ll, ll, ll, dp], i32),
         "pdsp_set_upfirdn_tile": ([i32], i32),
         "pdsp_dev_upfirdn_tile": ([ll, ll, ll, ll, i32, C.POINTER(ll)], i32),
+        "pdsp_dev_complex_op_vec4": ([i32, ll, vp, vp, vp, vp, ll, vp, vp, C.POINTER(i32)], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -559,6 +559,9 @@ def phase(re: torch.Tensor, im: torch.Tensor, out: torch.Tensor | None = None) -
 
 
 # -- element-wise complex vector arithmetic (src/math/complex.ts) on device rows ------
+# `out` may be `a`, or a `b` as long as `a` (plane on plane: each element is read before it is written); any other
+# overlap, and a broadcast row taken from `out` (X.div((X.re[0], X.im[0])): clone the row first), raises
+# PdspError "output overlaps input" (include/pdsp_hip.h).
 
 def _complex_op(name, a, b=None, s_re=0.0, s_im=0.0, out=None):
     are, aim = a

@@ -495,6 +495,44 @@ inline bool host_ranges_overlap(const void *a, size_t a_bytes, const void *b, si
   return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
+// a*b + c without overflow into *out
+inline bool mad_ok(long long a, long long b, long long c, long long *out) {
+  long long p;
+  return !__builtin_mul_overflow(a, b, &p) && !__builtin_add_overflow(p, c, out);
+}
+
+// The element-wise kernels read index i of every input before they write index i and touch no other index, so an
+// output may share bytes with an input of the same extent only where the two begin at the same address.
+inline bool elementwise_clash(const void *out, const void *in, size_t bytes) {
+  return out != in && host_ranges_overlap(out, bytes, in, bytes);
+}
+
+template <typename T>
+int apply_window_checked(long long batch, long long n, const T *in, const T *window, T *out, hipStream_t s) {
+  if (batch < 0 || n < 0) return fail(PDSP_ERR_BAD_ARG, "negative size");
+  long long total = 0;
+  if (!mad_ok(batch, n, 0, &total) || total > (LLONG_MAX / 8))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x n overflows", batch);
+  if (total == 0) return PDSP_OK;
+  if (!in || !window || !out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  const size_t bytes = (size_t)total * sizeof(T);
+  if (elementwise_clash(out, in, bytes) || host_ranges_overlap(out, bytes, window, (size_t)n * sizeof(T)))
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
+  return apply_window_dev<T>(batch, n, in, window, out, s);
+}
+
+template <typename T, bool PHASE>
+int polar_checked(long long count, const T *re, const T *im, T *out, hipStream_t s) {
+  if (count < 0) return fail(PDSP_ERR_BAD_ARG, "negative size");
+  if (count > (LLONG_MAX / 8)) return fail(PDSP_ERR_BAD_ARG, "count %lld overflows", count);
+  if (count == 0) return PDSP_OK;
+  if (!re || !im || !out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  const size_t bytes = (size_t)count * sizeof(T);
+  if (elementwise_clash(out, re, bytes) || elementwise_clash(out, im, bytes))
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
+  return polar_dev<T, PHASE>(count, re, im, out, s);
+}
+
 struct ChunkJob {
   long long first = 0, count = 0;  // rows [first, first + count) of the call
   int slot = 0;                    // staging slot of the worker that runs it
@@ -1203,14 +1241,13 @@ int pdsp_planes_free(pdsp_arena *arena) {
   }                                                                                                                \
   int pdsp_apply_window_##SUFFIX(long long batch, long long n, const T *in, const T *window, T *out,               \
                                  pdsp_stream stream) {                                                             \
-    if (batch < 0 || n < 0) return fail(PDSP_ERR_BAD_ARG, "negative size");                                        \
-    return apply_window_dev<T>(batch, n, in, window, out, (hipStream_t)stream);                                    \
+    return apply_window_checked<T>(batch, n, in, window, out, (hipStream_t)stream);                                \
   }                                                                                                                \
   int pdsp_magnitude_##SUFFIX(long long count, const T *re, const T *im, T *out, pdsp_stream stream) {             \
-    return polar_dev<T, false>(count, re, im, out, (hipStream_t)stream);                                           \
+    return polar_checked<T, false>(count, re, im, out, (hipStream_t)stream);                                       \
   }                                                                                                                \
   int pdsp_phase_##SUFFIX(long long count, const T *re, const T *im, T *out, pdsp_stream stream) {                 \
-    return polar_dev<T, true>(count, re, im, out, (hipStream_t)stream);                                            \
+    return polar_checked<T, true>(count, re, im, out, (hipStream_t)stream);                                        \
   }                                                                                                                \
   int pdsp_spectrum_##SUFFIX(const pdsp_plan *plan, long long batch, const T *frames, long long frame_len,         \
                              long long frame_stride, const T *window, int sides, T *amp_out, T *phase_out,         \
@@ -1228,6 +1265,7 @@ int pdsp_complex_op_f32(int op, long long count, const float *a_re, const float 
                         const float *b_im, long long b_len, double s_re, double s_im, float *out_re, float *out_im,
                         pdsp_stream stream) {
   if (count < 0) return fail(PDSP_ERR_BAD_ARG, "negative size");
+  if (count > (LLONG_MAX / 8)) return fail(PDSP_ERR_BAD_ARG, "count %lld overflows", count);
   if (op < PDSP_CX_ADD || op > PDSP_CX_MUL_SCALAR) return fail(PDSP_ERR_BAD_ARG, "unknown complex op %d", op);
   if (count == 0) return PDSP_OK;
   if (!a_re || !a_im || !out_re || !out_im) return fail(PDSP_ERR_BAD_ARG, "null buffer");
@@ -1237,6 +1275,18 @@ int pdsp_complex_op_f32(int op, long long count, const float *a_re, const float 
     if (b_len <= 0 || count % b_len != 0)
       return fail(PDSP_ERR_BAD_ARG, "second operand length %lld must divide %lld", b_len, count);
   }
+  // out may share bytes with a, or with a b of the same extent, only plane on plane (elementwise_clash): exact in
+  // place, a == b == out, and out_re / out_im on a_im / a_re.  A broadcast b is read by every row: it shares nothing.
+  const size_t bytes = (size_t)count * sizeof(float), b_bytes = (size_t)b_len * sizeof(float);
+  const auto b_clash = [&](const float *o, const float *b) {
+    return b_len == count ? elementwise_clash(o, b, bytes) : host_ranges_overlap(o, bytes, b, b_bytes);
+  };
+  bool clash = host_ranges_overlap(out_re, bytes, out_im, bytes);
+  for (const float *o : {out_re, out_im}) {
+    clash = clash || elementwise_clash(o, a_re, bytes) || elementwise_clash(o, a_im, bytes);
+    if (binary) clash = clash || b_clash(o, b_re) || b_clash(o, b_im);
+  }
+  if (clash) return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
   hipStream_t s = (hipStream_t)stream;
   const float sr = (float)s_re, si = (float)s_im;
   return complex_op_f32(op, count, a_re, a_im, b_re, b_im, b_len, sr, si, out_re, out_im, s);
@@ -1481,12 +1531,6 @@ int fir_spectrum_t(const pdsp_plan *plan, const T *taps, long long ntaps, T *h_r
   DeviceGuard g(plan->device);
   PDSP_HIP_TRY(g.err);
   return fir_spectrum_dev<T>(plan, taps, (int)ntaps, h_re, h_im, s);
-}
-
-// a*b + c without overflow into *out
-inline bool mad_ok(long long a, long long b, long long c, long long *out) {
-  long long p;
-  return !__builtin_mul_overflow(a, b, &p) && !__builtin_add_overflow(p, c, out);
 }
 
 template <typename T>
@@ -2163,6 +2207,14 @@ int pdsp_set_upfirdn_tile(int mode) {
   const int prev = g_upfirdn_tile;
   if (mode >= 0 && (mode & 15) <= 4) g_upfirdn_tile = mode;
   return prev;
+}
+
+int pdsp_dev_complex_op_vec4(int op, long long count, const float *a_re, const float *a_im, const float *b_re,
+                             const float *b_im, long long b_len, const float *out_re, const float *out_im, int *vec4) {
+  if (!vec4) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  if (op < PDSP_CX_ADD || op > PDSP_CX_MUL_SCALAR) return fail(PDSP_ERR_BAD_ARG, "unknown complex op %d", op);
+  *vec4 = complex_op_vec4(op <= PDSP_CX_DIV, count, a_re, a_im, b_re, b_im, b_len, out_re, out_im);
+  return PDSP_OK;
 }
 
 int pdsp_dev_upfirdn_tile(long long up, long long down, long long ntaps, long long y_len, int elem_bytes,

@@ -570,10 +570,7 @@ int run_interleaved(const pdsp_plan *plan, long long batch, const T *in, T *out,
 template <int OP>
 int launch_complex_op(long long count, const float *are, const float *aim, const float *bre, const float *bim,
                       long long b_len, float sre, float sim, float *ore, float *oim, hipStream_t s) {
-  const bool binary = OP <= pdsp::kDiv;
-  const bool vec4 = aligned(16, are, aim, ore, oim) && (!binary || aligned(16, bre, bim)) && count % 4 == 0 &&
-                    (!binary || b_len % 4 == 0);
-  if (vec4)
+  if (complex_op_vec4(OP <= pdsp::kDiv, count, are, aim, bre, bim, b_len, ore, oim))
     hipLaunchKernelGGL((pdsp::complex_op_kernel<float, OP, 4>), dim3(grid_for(count / 4)), dim3(256), 0, s, are, aim,
                        bre, bim, sre, sim, ore, oim, count, b_len);
   else

@@ -1363,10 +1363,11 @@ fourstep_out_kernel(const T *__restrict__ sre, const T *__restrict__ sim, T *__r
 
 // ---- element-wise kernels (stand-alone applyWindow / magnitude / phase) -----
 
+// `out` may be `in` (each index is read before it is written) and, in polar_kernel, `re` or `im`: those pointers
+// carry no __restrict__.  The entry points refuse every other overlap.
 template <typename T>
 __global__ void __launch_bounds__(256)
-apply_window_kernel(const T *__restrict__ in, const T *__restrict__ win, T *__restrict__ out,
-                    long long total, long long n) {
+apply_window_kernel(const T *in, const T *__restrict__ win, T *out, long long total, long long n) {
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step)
     out[i] = in[i] * win[i % n];
@@ -1374,13 +1375,18 @@ apply_window_kernel(const T *__restrict__ in, const T *__restrict__ win, T *__re
 
 template <typename T, bool PHASE>
 __global__ void __launch_bounds__(256)
-polar_kernel(const T *__restrict__ re, const T *__restrict__ im, T *__restrict__ out, long long total) {
+polar_kernel(const T *re, const T *im, T *out, long long total) {
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
     const T a = re[i], b = im[i];
     if constexpr (PHASE) out[i] = T(atan2(b, a));
     else if constexpr (sizeof(T) == 8) out[i] = hypot(a, b);  // Math.hypot, fourier.ts:106 (range-safe)
-    else out[i] = sqrt(a * a + b * b);                        // f32: |x| within ~1e-19 .. 1e19 (header)
+    else {
+      // f32: |x| within ~1e-19 .. 1e19 (header).  Both squares are exact in f64, so their sum is rounded to f32 once
+      // (u) and the correctly rounded sqrt halves that and adds half an ulp: below 1 ulp in all.  Three f32 roundings
+      // before the sqrt (2u) reach 1.5 ulp in the upper half of a binade (measured: 1.15 in 2^20 random pairs).
+      out[i] = sqrt((float)((double)a * (double)a + (double)b * (double)b));
+    }
   }
 }
 
@@ -1390,8 +1396,12 @@ polar_kernel(const T *__restrict__ re, const T *__restrict__ im, T *__restrict__
 // operand may be one row of `b_len` values broadcast over the batch (a filter response).
 enum ComplexOp { kAdd = 0, kSub = 1, kMul = 2, kDiv = 3, kConj = 4, kScale = 5, kMulScalar = 6 };
 
+// Every two-term sum is one explicit fma on one rounded product, and nothing else is contracted: left to the
+// compiler, the V = 4 and V = 1 instantiations of complex_op_kernel fused different halves of mul and div, and a
+// result depended in its last bit on the alignment of the operands.
 template <typename T, int OP>
 __device__ __forceinline__ void complex_op1(T ar, T ai, T br, T bi, T &orr, T &oi) {
+#pragma clang fp contract(off)
   if constexpr (OP == kAdd) {
     orr = ar + br;
     oi = ai + bi;
@@ -1399,12 +1409,14 @@ __device__ __forceinline__ void complex_op1(T ar, T ai, T br, T bi, T &orr, T &o
     orr = ar - br;
     oi = ai - bi;
   } else if constexpr (OP == kMul || OP == kMulScalar) {  // (ac - bd) + i(ad + bc)
-    orr = ar * br - ai * bi;
-    oi = ar * bi + ai * br;
+    const T p = ai * bi, q = ai * br;
+    orr = fma(ar, br, -p);
+    oi = fma(ar, bi, q);
   } else if constexpr (OP == kDiv) {  // ((ac + bd) + i(bc - ad)) / (c^2 + d^2), complex.ts:150-161
-    const T denom = br * br + bi * bi;
-    orr = (ar * br + ai * bi) / denom;
-    oi = (ai * br - ar * bi) / denom;
+    const T dd = bi * bi, p = ai * bi, q = ar * bi;
+    const T denom = fma(br, br, dd);
+    orr = fma(ar, br, p) / denom;
+    oi = fma(ai, br, -q) / denom;
   } else if constexpr (OP == kConj) {
     orr = ar;
     oi = -ai;
@@ -1436,7 +1448,7 @@ __device__ __forceinline__ void st_vec(T *p, long long i, const T (&v)[V]) {
 
 // No __restrict__: `out` may alias `a` (the fluent chain works in place) and `b` may be `out` too
 // (chain.mul(chain)); every thread reads its own index of a and b before it writes that index.  A
-// broadcast b (b_len < count) must not overlap `out`.
+// broadcast b (b_len < count) must not overlap `out`: pdsp_complex_op_f32 refuses that and every partial overlap.
 template <typename T, int OP, int V>  // V values per thread per step (4 = 16-byte accesses)
 __global__ void __launch_bounds__(256)
 complex_op_kernel(const T *are, const T *aim, const T *bre, const T *bim, T sre, T sim, T *ore, T *oim,

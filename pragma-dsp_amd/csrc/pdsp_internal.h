@@ -196,6 +196,15 @@ inline int grid_for(long long total) {
   return (int)b;
 }
 
+// launch_complex_op's choice between complex_op_kernel<T, OP, 4> (16-byte accesses: every plane the op uses on a
+// 16-byte boundary, count and a binary op's b_len multiples of 4) and <T, OP, 1>; pdsp_dev_complex_op_vec4 reports it.
+inline bool complex_op_vec4(bool binary, long long count, const void *are, const void *aim, const void *bre,
+                            const void *bim, long long b_len, const void *ore, const void *oim) {
+  const auto on16 = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
+  return on16(are) && on16(aim) && on16(ore) && on16(oim) && count % 4 == 0 &&
+         (!binary || (on16(bre) && on16(bim) && b_len % 4 == 0));
+}
+
 template <int V>
 using int_c = std::integral_constant<int, V>;
 
