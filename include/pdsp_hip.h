@@ -576,6 +576,38 @@ PDSP_API int pdsp_resample_poly_host_f64(const double *x, long long batch, long 
 PDSP_API int pdsp_upfirdn_host_f64(const double *h, long long ntaps, const double *x, long long batch, long long len,
                                    long long up, long long down, double *y);
 
+/* ---- any-length DFT (Bluestein's chirp-z algorithm), 2 <= L <= 4096, f32 / f64 ------------------ */
+/* The transform of rows whose length is NOT a power of two, with the conventions of numpy.fft.fft / numpy.fft.ifft
+ * along the last axis: X[k] = sum_n x[n] exp(-2 pi i n k / L), no scaling forward, 1/L on the inverse.  Rows are
+ * planar complex (re, im); a null im_in means real input (the same bits as a zero plane).  One launch per call: with
+ * the chirp c[n] = exp(-i pi n^2 / L) a row becomes a circular convolution of M = max(32, the power of two >= 2L - 1)
+ * points, X[k] = c[k] IFFT_M(FFT_M(x c) FFT_M(b))[k], b[j] = conj c[|j|], whose two M-point transforms run in LDS
+ * (pdsp_dft_conv_size() reports M).  The chirp and FFT_M(b) / M are built in f64 on the host (n^2 reduced mod 2L in
+ * integers) and rounded once per precision; they belong to the object and go to `device` (< 0: the current one) when
+ * it is created.
+ * Lengths: 2 <= L <= 4096, else PDSP_ERR_UNSUPPORTED_SIZE.  A power of two is accepted and takes the same kernel;
+ * pdsp_plan is the fast way for those (one transform of L points instead of two of >= 2L).
+ * f32 ~1e-7 * log2 M of max|X|, f64 ~1.6e-16 * log2 M (plus a few eps for the chirp products).
+ * Every argument is checked before any device work: a null handle or buffer (im_in excepted), batch < 1, strides < L,
+ * extents that overflow 64 bits or a grid of 2^31 rows give PDSP_ERR_BAD_ARG, and so does an output plane whose byte
+ * extent meets an input plane's -- except the exact in-place call re_out == re_in, im_out == im_in, out_stride ==
+ * in_stride with im_in non-null -- or the other output plane's. */
+typedef struct pdsp_dft pdsp_dft;
+PDSP_API int pdsp_dft_create(long long length, int device, pdsp_dft **out);
+PDSP_API int pdsp_dft_destroy(pdsp_dft *d);
+PDSP_API long long pdsp_dft_length(const pdsp_dft *d);
+PDSP_API long long pdsp_dft_conv_size(const pdsp_dft *d);
+/* `batch` rows of L points at in_stride elements -> rows of L bins at out_stride elements; inverse != 0: ifft */
+PDSP_API int pdsp_dft_c2c_f32(const pdsp_dft *d, long long batch, const float *re_in, const float *im_in,
+                              long long in_stride, float *re_out, float *im_out, long long out_stride, int inverse,
+                              pdsp_stream stream);
+PDSP_API int pdsp_dft_c2c_f64(const pdsp_dft *d, long long batch, const double *re_in, const double *im_in,
+                              long long in_stride, double *re_out, double *im_out, long long out_stride, int inverse,
+                              pdsp_stream stream);
+/* synchronous f64 host form: `batch` contiguous rows of `length` points in (im_in NULL: real), contiguous rows out */
+PDSP_API int pdsp_dft_host_f64(const double *re_in, const double *im_in, long long batch, long long length,
+                               int inverse, double *re_out, double *im_out);
+
 #ifdef __cplusplus
 }
 #endif

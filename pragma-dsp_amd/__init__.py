@@ -23,6 +23,7 @@ from .spectrum import SpectrumPeak, SpectrumResult, spectrum, spectrumBatch  # n
 from .stft import istft, stft  # noqa: F401
 from .dct import dct, idct  # noqa: F401
 from .hilbert import envelope, hilbert, instantaneous_phase  # noqa: F401
+from .dft import Dft, dft, idft  # noqa: F401
 from .resample import (  # noqa: F401
     Resampler,
     Upfirdn,
@@ -38,6 +39,6 @@ __all__ = [
     "FFT", "applyWindow", "binFrequencies", "createWindow", "fftShift", "fftShiftComplex",
     "magnitude", "phase", "spectrum", "spectrumBatch", "SpectrumPeak", "SpectrumResult", "PdspError",
     "FirFilter", "fir_filter", "firFilter", "stft", "istft", "dct", "idct",
-    "hilbert", "envelope", "instantaneous_phase",
+    "hilbert", "envelope", "instantaneous_phase", "Dft", "dft", "idft",
     "Resampler", "Upfirdn", "resample_poly", "upfirdn", "resamplePoly", "upfirdnHost", "design_taps",
 ]

@@ -156,6 +156,13 @@ def _load() -> C.CDLL:
         "pdsp_resample_design_f64": ([ll, ll, dp, C.POINTER(ll)], i32),
         "pdsp_resample_poly_host_f64": ([dp, ll, ll, ll, ll, dp, ll, dp], i32),
         "pdsp_upfirdn_host_f64": ([dp, ll, dp, ll, ll, ll, ll, dp], i32),
+        "pdsp_dft_create": ([ll, i32, C.POINTER(vp)], i32),
+        "pdsp_dft_destroy": ([vp], i32),
+        "pdsp_dft_length": ([vp], ll),
+        "pdsp_dft_conv_size": ([vp], ll),
+        "pdsp_dft_c2c_f32": ([vp, ll, vp, vp, ll, vp, vp, ll, i32, vp], i32),
+        "pdsp_dft_c2c_f64": ([vp, ll, vp, vp, ll, vp, vp, ll, i32, vp], i32),
+        "pdsp_dft_host_f64": ([dp, dp, ll, ll, i32, dp, dp], i32),
         "pdsp_set_upfirdn_tile": ([i32], i32),
         "pdsp_dev_upfirdn_tile": ([ll, ll, ll, ll, i32, C.POINTER(ll)], i32),
         "pdsp_dev_complex_op_vec4": ([i32, ll, vp, vp, vp, vp, ll, vp, vp, C.POINTER(i32)], i32),

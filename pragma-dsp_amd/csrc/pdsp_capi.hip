@@ -2,8 +2,8 @@
 // reference's error texts, plan objects, kernel dispatch by size, and the
 // synchronous host-f64 entry points the JS drop-in binds.
 //
-// Host side only, one of the library's nine translation units: no kernel is instantiated here (the dispatchers it
-// calls -- run_complex, spectrum_impl, ... -- are declared in pdsp_internal.h and live in the eight
+// Host side only, one of the library's ten translation units: no kernel is instantiated here (the dispatchers it
+// calls -- run_complex, spectrum_impl, ... -- are declared in pdsp_internal.h and live in the nine
 // pdsp_kernels_*.hip units).
 //
 // Product path only: nothing here touches oracle/, and there is no CPU fallback --
@@ -2253,4 +2253,220 @@ int pdsp_upfirdn_host_f64(const double *h, long long ntaps, const double *x, lon
   pdsp_resampler *rs = nullptr;
   if (int rc = pdsp_resampler_create(-1, up, down, h, ntaps, 0, &rs)) return rc;
   return resample_host(rs, x, batch, len, 1, y);
+}
+
+/* ---- any-length DFT: Bluestein's chirp-z algorithm ----------------------------- */
+
+// A DFT of L points is its two tables: the chirp c[n] = exp(-i pi (n^2 mod 2L) / L) and Bt = FFT_M(b) / M of the
+// chirp filter b[j] = conj c[|j|], both evaluated in f64 on the host and rounded once per precision, plus the radix
+// table of the M-point transform (the tw_half of a plan of 2M points).  They go up at create time through the plans'
+// uploader into the object's own lists.
+struct pdsp_dft {
+  int device = -1;
+  long long length = 0, m = 0;
+  int log2m = 0;
+  Tables<float> t32;   // tw_half: the M-point radix table; owned: every allocation of this precision
+  Tables<double> t64;
+  float2 *c32 = nullptr, *bt32 = nullptr;
+  double2 *c64 = nullptr, *bt64 = nullptr;
+};
+
+namespace pdsp_host {
+
+constexpr long long kDftMinLength = 2, kDftMaxLength = 4096;
+
+int check_dft_length(long long length) {
+  if (length < kDftMinLength || length > kDftMaxLength)
+    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "DFT length must be %lld ... %lld, got %lld", kDftMinLength, kDftMaxLength,
+                length);
+  return PDSP_OK;
+}
+
+// M = max(32, the smallest power of two >= 2L - 1): the circular convolution must hold the 2L - 1 lags of the chirp
+// filter; 32 is the smallest row of the sixteen-points-per-thread layout
+int dft_log2m(long long length) {
+  const int l = ilog2ll(2 * length - 1);
+  return l < 5 ? 5 : l;
+}
+
+// c[n], n < L, in f64: the angle's numerator n^2 is reduced mod 2L in integers, so the argument of cos / sin stays
+// below 2 pi and carries no rounding of n^2
+std::vector<double2> dft_chirp(long long length) {
+  std::vector<double2> c((size_t)length);
+  for (long long n = 0; n < length; ++n) {
+    const double a = -M_PI * (double)((n * n) % (2 * length)) / (double)length;
+    c[(size_t)n] = double2{std::cos(a), std::sin(a)};
+  }
+  return c;
+}
+
+// Bt = FFT_M(b) / M, b[j] = conj c[|j|] at j and M - j for |j| < L, else 0.  Radix-2 decimation in time in long
+// double, every twiddle evaluated directly (no recurrence): built once per object, M <= 8192.
+std::vector<double2> dft_filter_spectrum(const std::vector<double2> &c, int log2m) {
+  const size_t m = (size_t)1 << log2m, len = c.size();
+  std::vector<long double> re(m, 0.0L), im(m, 0.0L);
+  auto rev = [&](size_t i) {
+    size_t r = 0;
+    for (int b = 0; b < log2m; ++b) r |= ((i >> b) & 1) << (log2m - 1 - b);
+    return r;
+  };
+  for (size_t j = 0; j < len; ++j) {
+    re[rev(j)] = c[j].x, im[rev(j)] = -c[j].y;
+    if (j) re[rev(m - j)] = c[j].x, im[rev(m - j)] = -c[j].y;
+  }
+  const long double pi = 3.141592653589793238462643383279502884L;
+  for (size_t half = 1; half < m; half <<= 1) {
+    for (size_t k = 0; k < half; ++k) {
+      const long double a = -pi * (long double)k / (long double)half;
+      const long double wr = cosl(a), wi = sinl(a);
+      for (size_t i = k; i < m; i += 2 * half) {
+        const size_t j = i + half;
+        const long double tr = re[j] * wr - im[j] * wi, ti = re[j] * wi + im[j] * wr;
+        re[j] = re[i] - tr, im[j] = im[i] - ti;
+        re[i] += tr, im[i] += ti;
+      }
+    }
+  }
+  std::vector<double2> bt(m);
+  for (size_t k = 0; k < m; ++k) bt[k] = double2{(double)(re[k] / (long double)m), (double)(im[k] / (long double)m)};
+  return bt;
+}
+
+template <typename T2>
+std::vector<T2> dft_round(const std::vector<double2> &v) {
+  std::vector<T2> r(v.size());
+  for (size_t i = 0; i < v.size(); ++i) r[i].x = (decltype(r[i].x))v[i].x, r[i].y = (decltype(r[i].y))v[i].y;
+  return r;
+}
+
+template <typename T>
+hipError_t dft_upload(Tables<T> &t, int log2m, const std::vector<double2> &c, const std::vector<double2> &bt,
+                      typename pdsp::vec2<T>::type **c_out, typename pdsp::vec2<T>::type **bt_out) {
+  using T2 = typename pdsp::vec2<T>::type;
+  if (hipError_t e = upload_table(t, build_twiddles<T2>(log2m, pdsp::packed_log2e(log2m)), &t.tw_half)) return e;
+  if (hipError_t e = upload_table(t, dft_round<T2>(c), c_out)) return e;
+  return upload_table(t, dft_round<T2>(bt), bt_out);
+}
+
+template <typename T> struct DftView {
+  const Tables<T> &t;
+  const typename pdsp::vec2<T>::type *c, *bt;
+};
+template <typename T> DftView<T> dft_view(const pdsp_dft *d);
+template <> DftView<float> dft_view<float>(const pdsp_dft *d) { return {d->t32, d->c32, d->bt32}; }
+template <> DftView<double> dft_view<double>(const pdsp_dft *d) { return {d->t64, d->c64, d->bt64}; }
+
+template <typename T>
+int dft_t(const pdsp_dft *d, long long batch, const T *re_in, const T *im_in, long long in_stride, T *re_out, T *im_out,
+          long long out_stride, int inverse, hipStream_t s) {
+  if (!d) return fail(PDSP_ERR_BAD_ARG, "dft is null");
+  const long long n = d->length;
+  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
+  if (in_stride < n || out_stride < n)
+    return fail(PDSP_ERR_BAD_ARG, "strides must be >= L = %lld, got in_stride %lld, out_stride %lld", n, in_stride,
+                out_stride);
+  long long ic = 0, oc = 0;
+  if (!mad_ok(batch - 1, in_stride, n, &ic) || !mad_ok(batch - 1, out_stride, n, &oc) || ic > (LLONG_MAX / 8) ||
+      oc > (LLONG_MAX / 8))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+  if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  // exact in place is safe (a row is loaded in full by its own workgroup before that workgroup's first barrier, and a
+  // thread stores only the m it loaded); any other overlap would let one row's stores reach another row's loads, or
+  // one plane's stores the other plane's loads of the same row
+  const size_t ib = (size_t)ic * sizeof(T), ob = (size_t)oc * sizeof(T);
+  const bool in_place = im_in && (const void *)re_out == (const void *)re_in &&
+                        (const void *)im_out == (const void *)im_in && in_stride == out_stride;
+  if (!in_place && (host_ranges_overlap(re_out, ob, re_in, ib) || host_ranges_overlap(re_out, ob, im_in, ib) ||
+                    host_ranges_overlap(im_out, ob, re_in, ib) || host_ranges_overlap(im_out, ob, im_in, ib)))
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only re_out == re_in, im_out == im_in with equal strides "
+                                  "may share bytes)");
+  if (host_ranges_overlap(re_out, ob, im_out, ob))
+    return fail(PDSP_ERR_BAD_ARG, "the output planes overlap each other");
+  const DftView<T> v = dft_view<T>(d);
+  DeviceGuard dg(d->device);
+  PDSP_HIP_TRY(dg.err);
+  return dft_dev<T>(d->log2m, n, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, v.c, v.bt, v.t.tw_half,
+                    inverse != 0, s);
+}
+
+}  // namespace pdsp_host
+
+int pdsp_dft_create(long long length, int device, pdsp_dft **out) {
+  if (!out) return fail(PDSP_ERR_BAD_ARG, "out is null");
+  if (int rc = check_dft_length(length)) return rc;
+  if (int rc = require_device()) return rc;
+  int count = 0;
+  PDSP_HIP_TRY(hipGetDeviceCount(&count));
+  if (device < 0) PDSP_HIP_TRY(hipGetDevice(&device));
+  if (device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", device, count);
+  DeviceGuard g(device);
+  PDSP_HIP_TRY(g.err);
+  pdsp_dft *d = new (std::nothrow) pdsp_dft();
+  if (!d) return fail(PDSP_ERR_BAD_ARG, "out of host memory");
+  d->device = device, d->length = length, d->log2m = dft_log2m(length), d->m = 1LL << d->log2m;
+  const std::vector<double2> c = dft_chirp(length), bt = dft_filter_spectrum(c, d->log2m);
+  hipError_t e = dft_upload<float>(d->t32, d->log2m, c, bt, &d->c32, &d->bt32);
+  if (e == hipSuccess) e = dft_upload<double>(d->t64, d->log2m, c, bt, &d->c64, &d->bt64);
+  if (e != hipSuccess) {
+    pdsp_dft_destroy(d);
+    return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the DFT tables", (int)e,
+                hipGetErrorString(e));
+  }
+  *out = d;
+  return PDSP_OK;
+}
+
+int pdsp_dft_destroy(pdsp_dft *d) {
+  if (!d) return PDSP_OK;
+  {
+    DeviceGuard g(d->device);
+    d->t32.release();
+    d->t64.release();
+  }
+  delete d;
+  return PDSP_OK;
+}
+
+long long pdsp_dft_length(const pdsp_dft *d) { return d ? d->length : 0; }
+long long pdsp_dft_conv_size(const pdsp_dft *d) { return d ? d->m : 0; }
+
+int pdsp_dft_c2c_f32(const pdsp_dft *d, long long batch, const float *re_in, const float *im_in, long long in_stride,
+                     float *re_out, float *im_out, long long out_stride, int inverse, pdsp_stream stream) {
+  return dft_t<float>(d, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, inverse, (hipStream_t)stream);
+}
+int pdsp_dft_c2c_f64(const pdsp_dft *d, long long batch, const double *re_in, const double *im_in, long long in_stride,
+                     double *re_out, double *im_out, long long out_stride, int inverse, pdsp_stream stream) {
+  return dft_t<double>(d, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, inverse, (hipStream_t)stream);
+}
+
+// The host form rides the packed features' scaffold on the cached plan of 2M points (64 ... 16384: its stream, its
+// lock, its device); the DFT's own tables live for the call.  Buffer: out re | out im | in re | in im.
+int pdsp_dft_host_f64(const double *re_in, const double *im_in, long long batch, long long length, int inverse,
+                      double *re_out, double *im_out) {
+  if (int rc = check_dft_length(length)) return rc;
+  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
+  long long count = 0;
+  if (batch > 0x7fffffffLL || !mad_ok(batch, length, 0, &count) || count > (1LL << 40))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x %lld overflows", batch, length);
+  if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  const size_t nx = (size_t)count;
+  struct Owner {
+    pdsp_dft *p = nullptr;
+    ~Owner() { pdsp_dft_destroy(p); }
+  } own;
+  return packed_host_call(
+      2LL << dft_log2m(length), PDSP_WIN_RECT, 4 * nx,
+      [&](pdsp_plan *plan, hipStream_t s, const double *, double *d) -> int {
+        if (int rc = pdsp_dft_create(length, plan->device, &own.p)) return rc;
+        PDSP_HIP_TRY(hipMemcpyAsync(d + 2 * nx, re_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
+        if (im_in) PDSP_HIP_TRY(hipMemcpyAsync(d + 3 * nx, im_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
+        return dft_t<double>(own.p, batch, d + 2 * nx, im_in ? d + 3 * nx : nullptr, length, d, d + nx, length, inverse,
+                             s);
+      },
+      [&](const double *d) -> int {
+        PDSP_HIP_TRY(hipMemcpy(re_out, d, nx * sizeof(double), hipMemcpyDeviceToHost));
+        PDSP_HIP_TRY(hipMemcpy(im_out, d + nx, nx * sizeof(double), hipMemcpyDeviceToHost));
+        return PDSP_OK;
+      });
 }

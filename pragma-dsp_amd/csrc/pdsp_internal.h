@@ -1,6 +1,6 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from nine translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from ten translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
@@ -12,6 +12,7 @@
 //   pdsp_kernels_dct.hip          DCT-II and DCT-III, f32 and f64
 //   pdsp_kernels_hilbert.hip      Hilbert transform, analytic signal, envelope and phase, f32 and f64
 //   pdsp_kernels_resample.hip     polyphase rate change (upfirdn / resample_poly), f32 and f64
+//   pdsp_kernels_dft.hip          any-length DFT (Bluestein's chirp-z algorithm), f32 and f64
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -323,5 +324,15 @@ bool upfirdn_tile(long long up, long long down, long long ntaps, long long y_len
 extern int g_upfirdn_tile;
 // upfirdn_tile, or PDSP_ERR_UNSUPPORTED_SIZE with a message that names a forced instantiation
 int upfirdn_tile_checked(long long up, long long down, long long ntaps, long long y_len, size_t elem, UpfirdnTile *out);
+
+// pdsp_dft_c2c_* after validation (pdsp_kernels_dft.hip): 2 <= len <= 4096, M = 2^log2m = max(32, the power of two >=
+// 2 len - 1), 1 <= batch < 2^31, strides >= len, im_in null for real rows; chirp: c[n], len entries; bt: FFT_M(b) / M, M
+// entries; tw: the radix table of the M-point transform (the tw_half layout).  Exact in place is allowed, no other
+// overlap.
+template <typename T>
+int dft_dev(int log2m, long long len, long long batch, const T *re_in, const T *im_in, long long in_stride, T *re_out,
+            T *im_out, long long out_stride, const typename pdsp::vec2<T>::type *chirp,
+            const typename pdsp::vec2<T>::type *bt, const typename pdsp::vec2<T>::type *tw, bool inverse,
+            hipStream_t s);
 
 }  // namespace pdsp_host

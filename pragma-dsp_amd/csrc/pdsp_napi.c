@@ -721,6 +721,31 @@ static napi_value Hilbert(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* dft(inverse, re, im, outRe, outIm): the DFT (inverse != 0: the inverse DFT) of one row of re.length points, any
+ * length 2 ... 4096; im null or undefined means a real row.  The integer is read first and the typed-array pointers
+ * last, as in dct().  A length the library refuses reaches it unchanged (it fails before touching the outputs), so its
+ * message is what the caller sees. */
+static napi_value Dft(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return NULL;
+  int64_t inverse;
+  double *re, *im, *ore, *oim;
+  size_t nre, nim, nore, noim;
+  if (!get_i64(env, argv[0], &inverse) || !f64_array(env, argv[1], &re, &nre) || !f64_array(env, argv[2], &im, &nim) ||
+      !f64_array(env, argv[3], &ore, &nore) || !f64_array(env, argv[4], &oim, &noim))
+    return NULL;
+  if (im && nim != nre) {
+    napi_throw_error(env, NULL, "pdsp_napi: dft real and imag lengths differ");
+    return NULL;
+  }
+  if (nre >= 2 && nre <= 4096 && (nore < nre || noim < nre)) {
+    napi_throw_error(env, NULL, "pdsp_napi: dft output too small");
+    return NULL;
+  }
+  if (pdsp_dft_host_f64(re, im, 1, (long long)nre, inverse != 0, ore, oim) != PDSP_OK) return throw_pdsp(env);
+  return NULL;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   const struct {
     const char *name;
@@ -734,7 +759,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"nextPow2", NextPow2},     {"deviceCount", DeviceCount},
       {"firFilter", FirFilter},   {"resamplePoly", ResamplePoly}, {"upfirdn", Upfirdn},
       {"resampleDesign", ResampleDesign},   {"stft", Stft},               {"istft", Istft},
-      {"dct", Dct},                 {"hilbert", Hilbert},
+      {"dct", Dct},                 {"hilbert", Hilbert},         {"dft", Dft},
   };
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
     napi_value f;

@@ -6,6 +6,7 @@ import * as resampleNs from './resample';
 import * as stftNs from './stft';
 import * as dctNs from './dct';
 import * as hilbertNs from './hilbert';
+import * as dftNs from './dft';
 
 export { spectrum, spectrumBatch, spectrumStream, SpectrumOptions, SpectrumPeak, SpectrumResult } from './spectrum';
 export { ComplexArray } from './core';
@@ -14,6 +15,7 @@ export { FirMode, FirFilterOptions } from './filters';
 export { StftWindow, StftOptions, StftResult } from './stft';
 export { DctType, DctNorm, DctOptions } from './dct';
 export { HilbertOptions, AnalyticSignal } from './hilbert';
+export { DftResult } from './dft';
 
 export const core: {
   createComplexArray: typeof coreNs.createComplexArray;
@@ -49,4 +51,8 @@ export const hilbert: {
   hilbert: typeof hilbertNs.hilbert;
   envelope: typeof hilbertNs.envelope;
   instantaneousPhase: typeof hilbertNs.instantaneousPhase;
+};
+export const dft: {
+  dft: typeof dftNs.dft;
+  idft: typeof dftNs.idft;
 };

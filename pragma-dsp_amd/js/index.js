@@ -7,6 +7,7 @@
 //   require('.../js').stft       -> pragma-dsp/xform/stft (ROADMAP.md, "A) STFT")
 //   require('.../js').dct        -> pragma-dsp/xform/dct (ROADMAP.md, v0.3)
 //   require('.../js').hilbert    -> the Hilbert / analytic signal helpers (ROADMAP.md, v0.3)
+//   require('.../js').dft        -> the DFT of any length 2 ... 4096 (an extension: the reference has powers of two only)
 const core = require('./core');
 const fourier = require('./fourier');
 const s = require('./spectrum');
@@ -15,6 +16,7 @@ const stft = require('./stft');
 const dct = require('./dct');
 const hilbert = require('./hilbert');
 const resample = require('./resample');
+const dft = require('./dft');
 
 module.exports = {
   spectrum: s.spectrum,
@@ -61,5 +63,10 @@ Object.defineProperty(module.exports, 'dct', {
 // Hilbert / analytic signal helpers: planned by the reference (ROADMAP.md, v0.3), not enumerated for the same reason.
 Object.defineProperty(module.exports, 'hilbert', {
   value: { hilbert: hilbert.hilbert, envelope: hilbert.envelope, instantaneousPhase: hilbert.instantaneousPhase },
+  enumerable: false,
+});
+// Any-length DFT: an extension beside the reference's power-of-two Radix2Fft, not enumerated for the same reason.
+Object.defineProperty(module.exports, 'dft', {
+  value: { dft: dft.dft, idft: dft.idft },
   enumerable: false,
 });
