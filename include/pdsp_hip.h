@@ -608,6 +608,56 @@ PDSP_API int pdsp_dft_c2c_f64(const pdsp_dft *d, long long batch, const double *
 PDSP_API int pdsp_dft_host_f64(const double *re_in, const double *im_in, long long batch, long long length,
                                int inverse, double *re_out, double *im_out);
 
+/* ---- multi-level discrete wavelet transform (wavedec / waverec), orthogonal filters, f32 / f64 -- */
+/* h is a scaling filter of even length F, 2 <= F <= 32, and g[j] = (-1)^j h[F - 1 - j].  The extension is periodic, so
+ * a row of n samples has exactly n coefficients.  One analysis level on a row a of even length m:
+ *   cA[k] = sum_{j < F} h[j] a[(2k + j) mod m],   cD[k] = sum_{j < F} g[j] a[(2k + j) mod m],   0 <= k < m / 2
+ * (j ascending, one fma per term from +0).  The forward transform of J levels writes the Mallat layout
+ * [cA_J | cD_J | cD_{J-1} | ... | cD_1] into one row of n; n must be a positive multiple of 2^J (not a power of two:
+ * 96 with J = 5 is legal), and F may exceed a level's length (the index wraps more than once).  The inverse of a level
+ * is the transpose, for the output pair (2i, 2i + 1) with m' = m / 2:
+ *   x[2i]     = sum_{t < F/2} ( h[2t]     cA[(i - t) mod m'] + g[2t]     cD[(i - t) mod m'] )
+ *   x[2i + 1] = sum_{t < F/2} ( h[2t + 1] cA[(i - t) mod m'] + g[2t + 1] cD[(i - t) mod m'] )
+ * (t ascending, the cA term before the cD term, fma from +0).  A value's bits depend on the taps and the samples
+ * alone, not on the path, the tile, the batch or the stride.
+ * Wavelets: the names "haar" (= "db1") and "db2" ... "db10" -- Daubechies' extremal-phase filters, sum h = sqrt 2,
+ * db2 = [(1 + sqrt 3), (3 + sqrt 3), (3 - sqrt 3), (1 - sqrt 3)] / (4 sqrt 2) -- or the caller's own taps (name NULL),
+ * accepted only if |sum_k h[k] h[k + 2m] - delta_m| <= 1e-10 for every m (the inverse is the transpose only then);
+ * anything else is PDSP_ERR_BAD_ARG.  The taps are rounded once per precision and belong to the object.
+ * Every call is one launch.  A row whose levels fit one workgroup's LDS runs there whole, to any depth, and may be
+ * transformed exactly in place (y == x, equal strides).  Longer rows are cut into tiles with a halo; there the forward
+ * transform takes max((F - 2)(2^J - 1), 2^J) <= 32 KiB of values (8192 f32, 4096 f64; the inverse: 2^J alone), else
+ * PDSP_ERR_UNSUPPORTED_SIZE -- pdsp_dwt_max_levels() reports the deepest J for a row -- and any overlap of input and
+ * output is refused.  Checked before any device work: null handle or buffers, batch < 0, len not a positive multiple
+ * of 2^J, strides < len, extents that overflow 64 bits, a grid beyond 2^31 - 1 tiles, overlap (PDSP_ERR_BAD_ARG). */
+typedef struct pdsp_dwt pdsp_dwt;
+/* device < 0: arguments are checked without a device, the object binds to the device current at its first call */
+PDSP_API int pdsp_dwt_create(int device, const char *name_or_null, const double *taps_or_null, long long ntaps,
+                             int levels, pdsp_dwt **out);
+PDSP_API int pdsp_dwt_destroy(pdsp_dwt *w);
+PDSP_API long long pdsp_dwt_ntaps(const pdsp_dwt *w);
+PDSP_API int pdsp_dwt_levels(const pdsp_dwt *w);
+PDSP_API int pdsp_dwt_taps(const pdsp_dwt *w, double *taps); /* h, ntaps values */
+/* the taps of a built-in wavelet: *ntaps receives F; out may be NULL (query F), else holds >= 20 values */
+PDSP_API int pdsp_wavelet_taps(const char *name, double *out, long long *ntaps);
+/* the deepest forward transform of rows of `len` values of elem_bytes (4 or 8) with ntaps taps: the largest J with
+ * len mod 2^J == 0 that pdsp_dwt_forward_* takes; 0 for arguments outside the domain.  Needs no device. */
+PDSP_API int pdsp_dwt_max_levels(long long ntaps, long long len, int elem_bytes);
+/* `batch` rows of len samples at x_stride elements -> rows of len coefficients at y_stride elements, and back */
+PDSP_API int pdsp_dwt_forward_f32(const pdsp_dwt *w, long long batch, const float *x, long long len,
+                                  long long x_stride, float *y, long long y_stride, pdsp_stream stream);
+PDSP_API int pdsp_dwt_forward_f64(const pdsp_dwt *w, long long batch, const double *x, long long len,
+                                  long long x_stride, double *y, long long y_stride, pdsp_stream stream);
+PDSP_API int pdsp_dwt_inverse_f32(const pdsp_dwt *w, long long batch, const float *c, long long len,
+                                  long long c_stride, float *x, long long x_stride, pdsp_stream stream);
+PDSP_API int pdsp_dwt_inverse_f64(const pdsp_dwt *w, long long batch, const double *c, long long len,
+                                  long long c_stride, double *x, long long x_stride, pdsp_stream stream);
+/* synchronous f64 host forms: `batch` contiguous rows of len values in and out; name NULL: the caller's taps */
+PDSP_API int pdsp_dwt_forward_host_f64(const double *x, long long batch, long long len, const char *name_or_null,
+                                       const double *taps_or_null, long long ntaps, int levels, double *y);
+PDSP_API int pdsp_dwt_inverse_host_f64(const double *c, long long batch, long long len, const char *name_or_null,
+                                       const double *taps_or_null, long long ntaps, int levels, double *x);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,20 @@ PDSP_API int pdsp_set_upfirdn_tile(int mode);
 PDSP_API int pdsp_dev_upfirdn_tile(long long up, long long down, long long ntaps, long long y_len, int elem_bytes,
                                    long long info[9]);
 
+/* The path and tile of the wavelet transform (pdsp_dwt_*), forced.  mode & 3: 0 (default) = the rule,
+ * 1 = the resident path (rows up to 160 KiB of LDS), 2 = the tiled path.  mode >> 2 caps T, the positions per tile:
+ * 0 = no cap, n = at most n rounded up to a multiple of 2^levels.  A forced path is never replaced: where it does not
+ * fit (a row beyond LDS, a depth beyond the tiled path's limit) the call fails with PDSP_ERR_UNSUPPORTED_SIZE before
+ * any launch.  Results are bit-identical for every value; tests use it to run both paths, and many small tiles whose
+ * halo wraps round the row, on small inputs.  A mode that is negative or names no path leaves the setting as it is.
+ * Returns the previous value. */
+PDSP_API int pdsp_set_dwt_tile(int mode);
+/* What a pdsp_dwt_forward_* (inverse = 0) or pdsp_dwt_inverse_* (inverse = 1) call would launch under the current
+ * pdsp_set_dwt_tile: info = resident (1 / 0), T, halo (forward: samples staged beyond T; inverse: coefficients in front
+ * of a tile per band), lds_bytes, tiles per row.  Needs no device.  len a positive multiple of 2^levels. */
+PDSP_API int pdsp_dev_dwt_tile(long long ntaps, int levels, long long len, int elem_bytes, int inverse,
+                               long long info[5]);
+
 /* Which complex_op_kernel instantiation a pdsp_complex_op_f32 call with these arguments launches: *vec4 = 1 for
  * four values per thread in 16-byte accesses (a_re, a_im, out_re, out_im, and for a binary op b_re, b_im, all on
  * 16-byte boundaries; count, and for a binary op b_len, multiples of 4), 0 for one value per thread.  The pointers

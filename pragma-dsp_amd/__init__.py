@@ -33,6 +33,7 @@ from .resample import (  # noqa: F401
     upfirdn,
     upfirdnHost,
 )
+from .wavelet import Dwt, wavedec, wavedecHost, wavelet_taps, waverec, waverecHost  # noqa: F401
 
 __all__ = [
     "ComplexArray", "Radix2Fft", "createComplexArray", "isPowerOfTwo", "nextPowerOfTwo",
@@ -41,4 +42,5 @@ __all__ = [
     "FirFilter", "fir_filter", "firFilter", "stft", "istft", "dct", "idct",
     "hilbert", "envelope", "instantaneous_phase", "Dft", "dft", "idft",
     "Resampler", "Upfirdn", "resample_poly", "upfirdn", "resamplePoly", "upfirdnHost", "design_taps",
+    "Dwt", "wavedec", "waverec", "wavedecHost", "waverecHost", "wavelet_taps",
 ]

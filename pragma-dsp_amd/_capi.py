@@ -163,7 +163,22 @@ def _load() -> C.CDLL:
         "pdsp_dft_c2c_f32": ([vp, ll, vp, vp, ll, vp, vp, ll, i32, vp], i32),
         "pdsp_dft_c2c_f64": ([vp, ll, vp, vp, ll, vp, vp, ll, i32, vp], i32),
         "pdsp_dft_host_f64": ([dp, dp, ll, ll, i32, dp, dp], i32),
+        "pdsp_dwt_create": ([i32, C.c_char_p, dp, ll, i32, C.POINTER(vp)], i32),
+        "pdsp_dwt_destroy": ([vp], i32),
+        "pdsp_dwt_ntaps": ([vp], ll),
+        "pdsp_dwt_levels": ([vp], i32),
+        "pdsp_dwt_taps": ([vp, dp], i32),
+        "pdsp_wavelet_taps": ([C.c_char_p, dp, C.POINTER(ll)], i32),
+        "pdsp_dwt_max_levels": ([ll, ll, i32], i32),
+        "pdsp_dwt_forward_f32": ([vp, ll, vp, ll, ll, vp, ll, vp], i32),
+        "pdsp_dwt_forward_f64": ([vp, ll, vp, ll, ll, vp, ll, vp], i32),
+        "pdsp_dwt_inverse_f32": ([vp, ll, vp, ll, ll, vp, ll, vp], i32),
+        "pdsp_dwt_inverse_f64": ([vp, ll, vp, ll, ll, vp, ll, vp], i32),
+        "pdsp_dwt_forward_host_f64": ([dp, ll, ll, C.c_char_p, dp, ll, i32, dp], i32),
+        "pdsp_dwt_inverse_host_f64": ([dp, ll, ll, C.c_char_p, dp, ll, i32, dp], i32),
         "pdsp_set_upfirdn_tile": ([i32], i32),
+        "pdsp_set_dwt_tile": ([i32], i32),
+        "pdsp_dev_dwt_tile": ([ll, i32, ll, i32, i32, C.POINTER(ll)], i32),
         "pdsp_dev_upfirdn_tile": ([ll, ll, ll, ll, i32, C.POINTER(ll)], i32),
         "pdsp_dev_complex_op_vec4": ([i32, ll, vp, vp, vp, vp, ll, vp, vp, C.POINTER(i32)], i32),
     }

@@ -1,6 +1,6 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from ten translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from eleven translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
@@ -13,6 +13,7 @@
 //   pdsp_kernels_hilbert.hip      Hilbert transform, analytic signal, envelope and phase, f32 and f64
 //   pdsp_kernels_resample.hip     polyphase rate change (upfirdn / resample_poly), f32 and f64
 //   pdsp_kernels_dft.hip          any-length DFT (Bluestein's chirp-z algorithm), f32 and f64
+//   pdsp_kernels_dwt.hip          multi-level wavelet transform (wavedec / waverec), f32 and f64
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -334,5 +335,22 @@ int dft_dev(int log2m, long long len, long long batch, const T *re_in, const T *
             T *im_out, long long out_stride, const typename pdsp::vec2<T>::type *chirp,
             const typename pdsp::vec2<T>::type *bt, const typename pdsp::vec2<T>::type *tw, bool inverse,
             hipStream_t s);
+
+// pdsp_dwt_forward_* / pdsp_dwt_inverse_* after validation (pdsp_kernels_dwt.hip): f even, 2 <= f <= 32, levels >= 1,
+// len a positive multiple of 2^levels, batch >= 1, strides >= len, batch * t.tiles < 2^31, no overlap (resident: the
+// exact in-place call excepted); hg: h | g, 2 f device values; t from dwt_tile_checked for the same call.
+struct DwtTile {
+  bool resident = false;
+  long long tile = 0, halo = 0, tiles = 0;
+  size_t lds_bytes = 0;
+};
+// pdsp_set_dwt_tile: bits 0-1 0 = the rule, 1 = resident, 2 = tiled; the rest a cap on the tile (0: none)
+extern int g_dwt_tile;
+// The path and tile of one launch (the rule: pdsp_kernels_dwt.hip), or PDSP_ERR_UNSUPPORTED_SIZE
+int dwt_tile_checked(long long f, long long levels, long long n, size_t elem, bool inverse, DwtTile *out);
+int dwt_tiled_max_levels(long long f, size_t elem);
+template <typename T>
+int dwt_dev(const DwtTile &t, const T *hg, int f, int levels, bool inverse, long long batch, const T *in, long long len,
+            long long in_stride, T *out, long long out_stride, hipStream_t s);
 
 }  // namespace pdsp_host

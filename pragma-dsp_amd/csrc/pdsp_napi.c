@@ -746,6 +746,56 @@ static napi_value Dft(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* dwt(mode, name, taps, levels, x, y): mode 0 = wavedec, 1 = waverec of one row of x.length values into y, with the
+ * built-in wavelet `name` (a string) or, name null, the caller's taps; mode 2 = the taps of `name` into y, returning
+ * their number (y of length 0 asks for the number alone).  The scalars are read first and the typed-array pointers
+ * last, as in dct().  Arguments the library refuses reach it unchanged (it fails before touching y), so its message
+ * is what the caller sees. */
+static napi_value Dwt(napi_env env, napi_callback_info info) {
+  napi_value argv[6], res;
+  if (!get_args(env, info, 6, argv)) return NULL;
+  int64_t mode, levels;
+  char name[40];
+  const char *namep = NULL;
+  napi_valuetype nt;
+  if (!get_i64(env, argv[0], &mode) || !get_i64(env, argv[3], &levels)) return NULL;
+  NAPI_OK_OR_THROW(env, napi_typeof(env, argv[1], &nt));
+  if (nt != napi_null && nt != napi_undefined) {
+    size_t got = 0;
+    if (napi_get_value_string_utf8(env, argv[1], name, sizeof(name), &got) != napi_ok) {
+      napi_throw_type_error(env, NULL, "pdsp_napi: expected a string");
+      return NULL;
+    }
+    namep = name;
+  }
+  double *h, *x, *y;
+  size_t nh, nx, ny;
+  if (!f64_array(env, argv[2], &h, &nh) || !f64_array(env, argv[4], &x, &nx) || !f64_array(env, argv[5], &y, &ny))
+    return NULL;
+  if (mode == 2) {
+    long long n = 0;
+    if (pdsp_wavelet_taps(namep, NULL, &n) != PDSP_OK) return throw_pdsp(env);
+    if (ny) {
+      if ((long long)ny < n) {
+        napi_throw_error(env, NULL, "pdsp_napi: dwt output too small");
+        return NULL;
+      }
+      if (pdsp_wavelet_taps(namep, y, &n) != PDSP_OK) return throw_pdsp(env);
+    }
+    NAPI_OK_OR_THROW(env, napi_create_int64(env, n, &res));
+    return res;
+  }
+  if (ny < nx) {
+    napi_throw_error(env, NULL, "pdsp_napi: dwt output too small");
+    return NULL;
+  }
+  if (levels < INT32_MIN || levels > INT32_MAX) levels = 0; /* refused by the library as "levels must be >= 1" */
+  const int rc = mode ? pdsp_dwt_inverse_host_f64(x, 1, (long long)nx, namep, h, (long long)nh, (int)levels, y)
+                      : pdsp_dwt_forward_host_f64(x, 1, (long long)nx, namep, h, (long long)nh, (int)levels, y);
+  if (rc != PDSP_OK) return throw_pdsp(env);
+  return NULL;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   const struct {
     const char *name;
@@ -760,6 +810,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"firFilter", FirFilter},   {"resamplePoly", ResamplePoly}, {"upfirdn", Upfirdn},
       {"resampleDesign", ResampleDesign},   {"stft", Stft},               {"istft", Istft},
       {"dct", Dct},                 {"hilbert", Hilbert},         {"dft", Dft},
+      {"dwt", Dwt},
   };
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
     napi_value f;

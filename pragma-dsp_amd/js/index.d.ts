@@ -7,6 +7,7 @@ import * as stftNs from './stft';
 import * as dctNs from './dct';
 import * as hilbertNs from './hilbert';
 import * as dftNs from './dft';
+import * as waveletNs from './wavelet';
 
 export { spectrum, spectrumBatch, spectrumStream, SpectrumOptions, SpectrumPeak, SpectrumResult } from './spectrum';
 export { ComplexArray } from './core';
@@ -55,4 +56,9 @@ export const hilbert: {
 export const dft: {
   dft: typeof dftNs.dft;
   idft: typeof dftNs.idft;
+};
+export const wavelet: {
+  wavedec: typeof waveletNs.wavedec;
+  waverec: typeof waveletNs.waverec;
+  waveletTaps: typeof waveletNs.waveletTaps;
 };

@@ -8,6 +8,7 @@
 //   require('.../js').dct        -> pragma-dsp/xform/dct (ROADMAP.md, v0.3)
 //   require('.../js').hilbert    -> the Hilbert / analytic signal helpers (ROADMAP.md, v0.3)
 //   require('.../js').dft        -> the DFT of any length 2 ... 4096 (an extension: the reference has powers of two only)
+//   require('.../js').wavelet    -> the multi-level wavelet transform (ROADMAP.md, "E) Wavelets")
 const core = require('./core');
 const fourier = require('./fourier');
 const s = require('./spectrum');
@@ -17,6 +18,7 @@ const dct = require('./dct');
 const hilbert = require('./hilbert');
 const resample = require('./resample');
 const dft = require('./dft');
+const wavelet = require('./wavelet');
 
 module.exports = {
   spectrum: s.spectrum,
@@ -68,5 +70,10 @@ Object.defineProperty(module.exports, 'hilbert', {
 // Any-length DFT: an extension beside the reference's power-of-two Radix2Fft, not enumerated for the same reason.
 Object.defineProperty(module.exports, 'dft', {
   value: { dft: dft.dft, idft: dft.idft },
+  enumerable: false,
+});
+// Wavelets: planned by the reference (ROADMAP.md, item E), not enumerated for the same reason.
+Object.defineProperty(module.exports, 'wavelet', {
+  value: { wavedec: wavelet.wavedec, waverec: wavelet.waverec, waveletTaps: wavelet.waveletTaps },
   enumerable: false,
 });
