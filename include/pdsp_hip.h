@@ -608,6 +608,60 @@ PDSP_API int pdsp_dft_c2c_f64(const pdsp_dft *d, long long batch, const double *
 PDSP_API int pdsp_dft_host_f64(const double *re_in, const double *im_in, long long batch, long long length,
                                int inverse, double *re_out, double *im_out);
 
+/* ---- chirp-z transform and zoom FFT (scipy.signal.czt / zoom_fft), f32 / f64 -------------------- */
+/* K points of the z-transform of a row x of L samples, on an arc of a circle, with scipy.signal.czt's definition
+ * along the last axis:
+ *   X[k] = sum_{n < L} x[n] a^-n w^(n k),  k = 0 ... K - 1,   w = exp(-2 pi i step),  a = radius exp(2 pi i start)
+ * i.e. the points z_k = a w^-k.  step and start are f64 numbers of TURNS (finite, below 2^53 in magnitude), radius a
+ * finite f64 > 0.  Only arcs are built, |w| = 1: a spiral's chirps w^(n^2/2) span hundreds of orders of magnitude at
+ * these lengths.  There is no inverse (the transform has no cheap one).  zoom_fft(fn = [f1, f2], m, fs, endpoint) is
+ * step = (f2 - f1) / (fs (m - 1 if endpoint else m)), start = f1 / fs; the DFT is K = L, step = 1 / L.
+ * The parameters are angles and not a complex w because the tables are the precision budget: their phases are formed
+ * exactly from the doubles given.  n^2 step and n start are error-free products (p = n2 * step, e = fma(n2, step, -p)),
+ * p is reduced with fmod -- mod 2 for the half-turn chirp, mod 1 for a's angle -- and e is added after the reduction,
+ * so the argument of cos / sin stays below 2 pi and nothing is lost at n^2 ~ 2^26.  Note that step = 1.0 / 1000 is the
+ * double NEAREST 1/1000, not 1/1000: in f64 the difference shows (about 1e-11 rad at the far corner n = k = 999);
+ * pdsp_dft is the way to the exact L-th roots of unity.
+ * One launch per call: with n k = (n^2 + k^2 - (k - n)^2) / 2,
+ *   X[k] = post[k] sum_n (x[n] pre[n]) b[k - n]
+ *   pre[n]  = a^-n w^(n^2/2)   (L entries)
+ *   post[k] = w^(k^2/2)        (K entries)
+ *   b[j]    = w^(-j^2/2)       for -(L - 1) <= j <= K - 1
+ * a circular convolution of M = max(32, the power of two >= L + K - 1) points (pdsp_czt_conv_size() reports M) with
+ * b[j] stored at index j for j >= 0, at index M + j for j < 0 and zero elsewhere, whose two M-point transforms run in
+ * LDS: X[k] = post[k] IFFT_M(FFT_M(x pre) FFT_M(b))[k].  pre, post and Bt = FFT_M(b) / M are evaluated in long double
+ * on the host and rounded once per precision; they belong to the object and go to `device` (< 0: the current one) when
+ * it is created.
+ * Limits: L >= 1, K >= 1, L + K - 1 <= 8192 (else PDSP_ERR_UNSUPPORTED_SIZE); radius^-(L-1) within [2^-64, 2^64],
+ * finite step / start / radius (else PDSP_ERR_BAD_ARG).  Argument errors of pdsp_czt_create are reported before any
+ * device work (device = -1 gets them on a machine without a GPU) and leave *out untouched.
+ * Rows are planar complex (re, im); a null im_in means real rows (the same bits as a zero plane).
+ * f32 ~1e-7 * log2 M, f64 ~1.6e-16 * log2 M (plus a few eps for the chirp products) of max(max|X|, ||x radius^-n||_2).
+ * Every argument is checked before any device work: a null handle or buffer (im_in excepted), batch < 1, in_stride < L,
+ * out_stride < K, extents that overflow 64 bits or a grid of 2^31 rows give PDSP_ERR_BAD_ARG.  Overlap: the exact
+ * in-place call is allowed -- re_out == re_in, im_out == im_in (real rows: an im_out of its own), out_stride ==
+ * in_stride (>= max(L, K) by the rule above); a workgroup loads all of its rows before its first barrier and stores
+ * only into those rows.  Every other meeting of an output plane's byte extent with an input plane's, or with the other
+ * output plane's, is PDSP_ERR_BAD_ARG. */
+typedef struct pdsp_czt pdsp_czt;
+PDSP_API int pdsp_czt_create(long long length, long long bins, double step, double start, double radius, int device,
+                             pdsp_czt **out);
+PDSP_API int pdsp_czt_destroy(pdsp_czt *c);
+PDSP_API long long pdsp_czt_length(const pdsp_czt *c);
+PDSP_API long long pdsp_czt_bins(const pdsp_czt *c);
+PDSP_API long long pdsp_czt_conv_size(const pdsp_czt *c);
+/* `batch` rows of L samples at in_stride elements -> rows of K points at out_stride elements */
+PDSP_API int pdsp_czt_f32(const pdsp_czt *c, long long batch, const float *re_in, const float *im_in,
+                          long long in_stride, float *re_out, float *im_out, long long out_stride, pdsp_stream stream);
+PDSP_API int pdsp_czt_f64(const pdsp_czt *c, long long batch, const double *re_in, const double *im_in,
+                          long long in_stride, double *re_out, double *im_out, long long out_stride,
+                          pdsp_stream stream);
+/* synchronous f64 host form: `batch` contiguous rows of `length` samples in (im_in NULL: real), contiguous rows of
+ * `bins` points out */
+PDSP_API int pdsp_czt_host_f64(const double *re_in, const double *im_in, long long batch, long long length,
+                               long long bins, double step, double start, double radius, double *re_out,
+                               double *im_out);
+
 /* ---- multi-level discrete wavelet transform (wavedec / waverec), orthogonal filters, f32 / f64 -- */
 /* h is a scaling filter of even length F, 2 <= F <= 32, and g[j] = (-1)^j h[F - 1 - j].  The extension is periodic, so
  * a row of n samples has exactly n coefficients.  One analysis level on a row a of even length m:

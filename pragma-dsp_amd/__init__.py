@@ -24,6 +24,7 @@ from .stft import istft, stft  # noqa: F401
 from .dct import dct, idct  # noqa: F401
 from .hilbert import envelope, hilbert, instantaneous_phase  # noqa: F401
 from .dft import Dft, dft, idft  # noqa: F401
+from .czt import Czt, czt, czt_points, zoom_fft  # noqa: F401
 from .resample import (  # noqa: F401
     Resampler,
     Upfirdn,
@@ -41,6 +42,7 @@ __all__ = [
     "magnitude", "phase", "spectrum", "spectrumBatch", "SpectrumPeak", "SpectrumResult", "PdspError",
     "FirFilter", "fir_filter", "firFilter", "stft", "istft", "dct", "idct",
     "hilbert", "envelope", "instantaneous_phase", "Dft", "dft", "idft",
+    "Czt", "czt", "zoom_fft", "czt_points",
     "Resampler", "Upfirdn", "resample_poly", "upfirdn", "resamplePoly", "upfirdnHost", "design_taps",
     "Dwt", "wavedec", "waverec", "wavedecHost", "waverecHost", "wavelet_taps",
 ]

@@ -163,6 +163,14 @@ def _load() -> C.CDLL:
         "pdsp_dft_c2c_f32": ([vp, ll, vp, vp, ll, vp, vp, ll, i32, vp], i32),
         "pdsp_dft_c2c_f64": ([vp, ll, vp, vp, ll, vp, vp, ll, i32, vp], i32),
         "pdsp_dft_host_f64": ([dp, dp, ll, ll, i32, dp, dp], i32),
+        "pdsp_czt_create": ([ll, ll, dbl, dbl, dbl, i32, C.POINTER(vp)], i32),
+        "pdsp_czt_destroy": ([vp], i32),
+        "pdsp_czt_length": ([vp], ll),
+        "pdsp_czt_bins": ([vp], ll),
+        "pdsp_czt_conv_size": ([vp], ll),
+        "pdsp_czt_f32": ([vp, ll, vp, vp, ll, vp, vp, ll, vp], i32),
+        "pdsp_czt_f64": ([vp, ll, vp, vp, ll, vp, vp, ll, vp], i32),
+        "pdsp_czt_host_f64": ([dp, dp, ll, ll, ll, dbl, dbl, dbl, dp, dp], i32),
         "pdsp_dwt_create": ([i32, C.c_char_p, dp, ll, i32, C.POINTER(vp)], i32),
         "pdsp_dwt_destroy": ([vp], i32),
         "pdsp_dwt_ntaps": ([vp], ll),

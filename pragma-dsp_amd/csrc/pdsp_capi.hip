@@ -2471,6 +2471,265 @@ int pdsp_dft_host_f64(const double *re_in, const double *im_in, long long batch,
       });
 }
 
+/* ---- chirp-z transform and zoom FFT --------------------------------------------- */
+
+// A chirp-z transform is its three tables -- pre[n] = a^-n w^(n^2/2), post[k] = w^(k^2/2) and Bt = FFT_M(b) / M of the
+// chirp filter b[j] = w^(-j^2/2) -- evaluated in long double on the host from exactly reduced phases and rounded once
+// per precision, plus the radix table of the M-point transform (the tw_half of a plan of 2M points).  They go up at
+// create time through the plans' uploader into the object's own lists.
+struct pdsp_czt {
+  int device = -1;
+  long long length = 0, bins = 0, m = 0;
+  int log2m = 0;
+  Tables<float> t32;   // tw_half: the M-point radix table; owned: every allocation of this precision
+  Tables<double> t64;
+  float2 *pre32 = nullptr, *post32 = nullptr, *bt32 = nullptr;
+  double2 *pre64 = nullptr, *post64 = nullptr, *bt64 = nullptr;
+};
+
+namespace pdsp_host {
+
+constexpr long long kCztMaxConv = 8192;
+
+int check_czt_args(long long length, long long bins, double step, double start, double radius) {
+  if (length < 1) return fail(PDSP_ERR_UNSUPPORTED_SIZE, "CZT length must be >= 1, got %lld", length);
+  if (bins < 1) return fail(PDSP_ERR_UNSUPPORTED_SIZE, "CZT bins must be >= 1, got %lld", bins);
+  if (length > kCztMaxConv || bins > kCztMaxConv || length + bins - 1 > kCztMaxConv)
+    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "CZT length + bins - 1 must be <= %lld, got %lld + %lld - 1", kCztMaxConv,
+                length, bins);
+  // (a double of 2^53 or more is a whole number of turns, or of half turns)
+  if (!(std::fabs(step) < 0x1p53) || !(std::fabs(start) < 0x1p53))
+    return fail(PDSP_ERR_BAD_ARG, "CZT step and start must be finite numbers of turns below 2^53, got %g and %g", step,
+                start);
+  if (!(radius > 0.0) || !std::isfinite(radius))
+    return fail(PDSP_ERR_BAD_ARG, "CZT radius must be finite and > 0, got %g", radius);
+  if (std::fabs((long double)(length - 1) * log2l((long double)radius)) > 64.0L)
+    return fail(PDSP_ERR_BAD_ARG, "CZT radius^-(L-1) must lie within [2^-64, 2^64], got radius %.17g at L = %lld",
+                radius, length);
+  return PDSP_OK;
+}
+
+// M = max(32, the smallest power of two >= L + K - 1): the circular convolution must hold the L + K - 1 lags
+// -(L - 1) ... K - 1 of the chirp filter; 32 is the smallest row of the sixteen-points-per-thread layout
+int czt_log2m(long long length, long long bins) {
+  const int l = ilog2ll(length + bins - 1);
+  return l < 5 ? 5 : l;
+}
+
+// (n t) mod `mod` in turns, exactly: n an integer below 2^27 (or its square), t the caller's double.  p + e is the
+// product without error; fmod of p is exact; the error term is added after the reduction, so the sum carries the
+// product's low bits however large n t is.
+long double czt_turns(long long n, double t, double mod) {
+  const double p = (double)n * t, e = std::fma((double)n, t, -p);
+  return (long double)std::fmod(p, mod) + (long double)e;
+}
+
+struct ldcx {
+  long double x, y;
+};
+constexpr long double kPiL = 3.141592653589793238462643383279502884L;
+
+// w^(sgn n^2 / 2), w = exp(-2 pi i step): the half-turn chirp, n^2 step reduced mod 2
+ldcx czt_chirp(long long n, double step, int sgn) {
+  const long double a = -(long double)sgn * kPiL * czt_turns(n * n, step, 2.0);
+  return ldcx{cosl(a), sinl(a)};
+}
+
+template <class F>
+std::vector<double2> czt_table(long long count, F f) {
+  std::vector<double2> t((size_t)count);
+  for (long long i = 0; i < count; ++i) {
+    const ldcx v = f(i);
+    t[(size_t)i] = double2{(double)v.x, (double)v.y};
+  }
+  return t;
+}
+
+// pre[n] = a^-n w^(n^2/2), a = radius exp(2 pi i start): n start reduced mod 1
+std::vector<double2> czt_pre(long long length, double step, double start, double radius) {
+  return czt_table(length, [&](long long n) {
+    const ldcx c = czt_chirp(n, step, 1);
+    const long double a = -2.0L * kPiL * czt_turns(n, start, 1.0), r = powl((long double)radius, -(long double)n);
+    const long double ar = r * cosl(a), ai = r * sinl(a);
+    return ldcx{ar * c.x - ai * c.y, ar * c.y + ai * c.x};
+  });
+}
+
+std::vector<double2> czt_post(long long bins, double step) {
+  return czt_table(bins, [&](long long k) { return czt_chirp(k, step, 1); });
+}
+
+// Bt = FFT_M(b) / M, b[j] = w^(-j^2/2) at j for 0 <= j < K, at M + j for -(L - 1) <= j < 0, else 0 (M >= L + K - 1:
+// the two runs do not meet).  b's support is not symmetric, so this is not dft_filter_spectrum's even filter; the
+// transform is the same: radix-2 decimation in time in long double, every twiddle evaluated directly.
+std::vector<double2> czt_filter_spectrum(long long length, long long bins, double step, int log2m) {
+  const size_t m = (size_t)1 << log2m;
+  std::vector<long double> re(m, 0.0L), im(m, 0.0L);
+  auto rev = [&](size_t i) {
+    size_t r = 0;
+    for (int b = 0; b < log2m; ++b) r |= ((i >> b) & 1) << (log2m - 1 - b);
+    return r;
+  };
+  for (long long j = -(length - 1); j < bins; ++j) {
+    const ldcx v = czt_chirp(j, step, -1);
+    const size_t at = rev((size_t)(j < 0 ? (long long)m + j : j));
+    re[at] = v.x, im[at] = v.y;
+  }
+  for (size_t half = 1; half < m; half <<= 1) {
+    for (size_t k = 0; k < half; ++k) {
+      const long double a = -kPiL * (long double)k / (long double)half;
+      const long double wr = cosl(a), wi = sinl(a);
+      for (size_t i = k; i < m; i += 2 * half) {
+        const size_t j = i + half;
+        const long double tr = re[j] * wr - im[j] * wi, ti = re[j] * wi + im[j] * wr;
+        re[j] = re[i] - tr, im[j] = im[i] - ti;
+        re[i] += tr, im[i] += ti;
+      }
+    }
+  }
+  std::vector<double2> bt(m);
+  for (size_t k = 0; k < m; ++k) bt[k] = double2{(double)(re[k] / (long double)m), (double)(im[k] / (long double)m)};
+  return bt;
+}
+
+template <typename T> struct CztView {
+  const Tables<T> &t;
+  const typename pdsp::vec2<T>::type *pre, *post, *bt;
+};
+template <typename T> CztView<T> czt_view(const pdsp_czt *c);
+template <> CztView<float> czt_view<float>(const pdsp_czt *c) { return {c->t32, c->pre32, c->post32, c->bt32}; }
+template <> CztView<double> czt_view<double>(const pdsp_czt *c) { return {c->t64, c->pre64, c->post64, c->bt64}; }
+
+template <typename T>
+int czt_t(const pdsp_czt *c, long long batch, const T *re_in, const T *im_in, long long in_stride, T *re_out, T *im_out,
+          long long out_stride, hipStream_t s) {
+  if (!c) return fail(PDSP_ERR_BAD_ARG, "czt is null");
+  const long long n = c->length, k = c->bins;
+  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
+  if (in_stride < n || out_stride < k)
+    return fail(PDSP_ERR_BAD_ARG, "strides must be >= L = %lld in and >= K = %lld out, got in_stride %lld, out_stride %lld",
+                n, k, in_stride, out_stride);
+  long long ic = 0, oc = 0;
+  if (!mad_ok(batch - 1, in_stride, n, &ic) || !mad_ok(batch - 1, out_stride, k, &oc) || ic > (LLONG_MAX / 8) ||
+      oc > (LLONG_MAX / 8))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
+  if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  // Exact in place is safe: a workgroup loads all of its rows in full before its first barrier and stores only into
+  // those rows, and with equal strides >= max(L, K) a row's samples and its bins share one slot that no other row
+  // touches.  Any other overlap would let one row's stores reach another row's loads, or one plane's stores the
+  // other plane's loads of the same row.  In place the two planes are compared over the larger of the two extents: the
+  // samples of the last row may reach past its bins.
+  const size_t ib = (size_t)ic * sizeof(T), ob = (size_t)oc * sizeof(T), xb = ib > ob ? ib : ob;
+  const bool in_place = (const void *)re_out == (const void *)re_in && in_stride == out_stride &&
+                        (!im_in || (const void *)im_out == (const void *)im_in);
+  const bool clash = in_place ? (im_in ? host_ranges_overlap(re_in, xb, im_in, xb) : host_ranges_overlap(im_out, ob, re_in, xb))
+                              : (host_ranges_overlap(re_out, ob, re_in, ib) || host_ranges_overlap(re_out, ob, im_in, ib) ||
+                                 host_ranges_overlap(im_out, ob, re_in, ib) || host_ranges_overlap(im_out, ob, im_in, ib));
+  if (clash)
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only re_out == re_in, im_out == im_in -- a real row's im_out "
+                                  "apart -- with equal strides may share bytes)");
+  if (host_ranges_overlap(re_out, ob, im_out, ob))
+    return fail(PDSP_ERR_BAD_ARG, "the output planes overlap each other");
+  const CztView<T> v = czt_view<T>(c);
+  DeviceGuard dg(c->device);
+  PDSP_HIP_TRY(dg.err);
+  return czt_dev<T>(c->log2m, n, k, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, v.pre, v.post, v.bt,
+                    v.t.tw_half, s);
+}
+
+}  // namespace pdsp_host
+
+int pdsp_czt_create(long long length, long long bins, double step, double start, double radius, int device,
+                    pdsp_czt **out) {
+  if (!out) return fail(PDSP_ERR_BAD_ARG, "out is null");
+  if (int rc = check_czt_args(length, bins, step, start, radius)) return rc;
+  if (int rc = require_device()) return rc;
+  int count = 0;
+  PDSP_HIP_TRY(hipGetDeviceCount(&count));
+  if (device < 0) PDSP_HIP_TRY(hipGetDevice(&device));
+  if (device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", device, count);
+  DeviceGuard g(device);
+  PDSP_HIP_TRY(g.err);
+  pdsp_czt *c = new (std::nothrow) pdsp_czt();
+  if (!c) return fail(PDSP_ERR_BAD_ARG, "out of host memory");
+  c->device = device, c->length = length, c->bins = bins, c->log2m = czt_log2m(length, bins), c->m = 1LL << c->log2m;
+  const std::vector<double2> pre = czt_pre(length, step, start, radius), post = czt_post(bins, step),
+                             bt = czt_filter_spectrum(length, bins, step, c->log2m);
+  auto upload = [&](auto &t, auto **pre_out, auto **post_out, auto **bt_out) -> hipError_t {
+    using T2 = std::remove_pointer_t<std::remove_pointer_t<decltype(pre_out)>>;
+    if (hipError_t e = upload_table(t, build_twiddles<T2>(c->log2m, pdsp::packed_log2e(c->log2m)), &t.tw_half)) return e;
+    if (hipError_t e = upload_table(t, dft_round<T2>(pre), pre_out)) return e;
+    if (hipError_t e = upload_table(t, dft_round<T2>(post), post_out)) return e;
+    return upload_table(t, dft_round<T2>(bt), bt_out);
+  };
+  hipError_t e = upload(c->t32, &c->pre32, &c->post32, &c->bt32);
+  if (e == hipSuccess) e = upload(c->t64, &c->pre64, &c->post64, &c->bt64);
+  if (e != hipSuccess) {
+    pdsp_czt_destroy(c);
+    return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the CZT tables", (int)e,
+                hipGetErrorString(e));
+  }
+  *out = c;
+  return PDSP_OK;
+}
+
+int pdsp_czt_destroy(pdsp_czt *c) {
+  if (!c) return PDSP_OK;
+  {
+    DeviceGuard g(c->device);
+    c->t32.release();
+    c->t64.release();
+  }
+  delete c;
+  return PDSP_OK;
+}
+
+long long pdsp_czt_length(const pdsp_czt *c) { return c ? c->length : 0; }
+long long pdsp_czt_bins(const pdsp_czt *c) { return c ? c->bins : 0; }
+long long pdsp_czt_conv_size(const pdsp_czt *c) { return c ? c->m : 0; }
+
+int pdsp_czt_f32(const pdsp_czt *c, long long batch, const float *re_in, const float *im_in, long long in_stride,
+                 float *re_out, float *im_out, long long out_stride, pdsp_stream stream) {
+  return czt_t<float>(c, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, (hipStream_t)stream);
+}
+int pdsp_czt_f64(const pdsp_czt *c, long long batch, const double *re_in, const double *im_in, long long in_stride,
+                 double *re_out, double *im_out, long long out_stride, pdsp_stream stream) {
+  return czt_t<double>(c, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, (hipStream_t)stream);
+}
+
+// The host form rides the packed features' scaffold on the cached plan of 2M points, as pdsp_dft_host_f64 does; the
+// transform's own tables live for the call.  Buffer: out re | out im | in re | in im.
+int pdsp_czt_host_f64(const double *re_in, const double *im_in, long long batch, long long length, long long bins,
+                      double step, double start, double radius, double *re_out, double *im_out) {
+  if (int rc = check_czt_args(length, bins, step, start, radius)) return rc;
+  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
+  long long cin = 0, cout = 0;
+  if (batch > 0x7fffffffLL || !mad_ok(batch, length, 0, &cin) || !mad_ok(batch, bins, 0, &cout) || cin > (1LL << 40) ||
+      cout > (1LL << 40))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x (%lld, %lld) overflows", batch, length, bins);
+  if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  const size_t nx = (size_t)cin, ny = (size_t)cout;
+  struct Owner {
+    pdsp_czt *p = nullptr;
+    ~Owner() { pdsp_czt_destroy(p); }
+  } own;
+  return packed_host_call(
+      2LL << czt_log2m(length, bins), PDSP_WIN_RECT, 2 * ny + 2 * nx,
+      [&](pdsp_plan *plan, hipStream_t s, const double *, double *d) -> int {
+        if (int rc = pdsp_czt_create(length, bins, step, start, radius, plan->device, &own.p)) return rc;
+        double *const xr = d + 2 * ny, *const xi = xr + nx;
+        PDSP_HIP_TRY(hipMemcpyAsync(xr, re_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
+        if (im_in) PDSP_HIP_TRY(hipMemcpyAsync(xi, im_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
+        return czt_t<double>(own.p, batch, xr, im_in ? xi : nullptr, length, d, d + ny, bins, s);
+      },
+      [&](const double *d) -> int {
+        PDSP_HIP_TRY(hipMemcpy(re_out, d, ny * sizeof(double), hipMemcpyDeviceToHost));
+        PDSP_HIP_TRY(hipMemcpy(im_out, d + ny, ny * sizeof(double), hipMemcpyDeviceToHost));
+        return PDSP_OK;
+      });
+}
+
 /* ---- multi-level wavelet transform: wavedec / waverec -------------------------- */
 
 // A wavelet transform is its scaling filter and its depth: no FFT size, so no plan.  The taps are kept in f64, h | g,

@@ -1,6 +1,6 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from eleven translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from twelve translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
@@ -14,6 +14,7 @@
 //   pdsp_kernels_resample.hip     polyphase rate change (upfirdn / resample_poly), f32 and f64
 //   pdsp_kernels_dft.hip          any-length DFT (Bluestein's chirp-z algorithm), f32 and f64
 //   pdsp_kernels_dwt.hip          multi-level wavelet transform (wavedec / waverec), f32 and f64
+//   pdsp_kernels_czt.hip          chirp-z transform and zoom FFT (czt / zoom_fft), f32 and f64
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -352,5 +353,15 @@ int dwt_tiled_max_levels(long long f, size_t elem);
 template <typename T>
 int dwt_dev(const DwtTile &t, const T *hg, int f, int levels, bool inverse, long long batch, const T *in, long long len,
             long long in_stride, T *out, long long out_stride, hipStream_t s);
+
+// pdsp_czt_* after validation (pdsp_kernels_czt.hip): len, bins >= 1, len + bins - 1 <= 8192, M = 2^log2m = max(32, the
+// power of two >= len + bins - 1), 1 <= batch < 2^31, in_stride >= len, out_stride >= bins, im_in null for real rows;
+// pre: a^-n w^(n^2/2), len entries; post: w^(k^2/2), bins entries; bt: FFT_M(b) / M, M entries; tw: the radix table of
+// the M-point transform (the tw_half layout).  Exact in place is allowed, no other overlap.
+template <typename T>
+int czt_dev(int log2m, long long len, long long bins, long long batch, const T *re_in, const T *im_in,
+            long long in_stride, T *re_out, T *im_out, long long out_stride, const typename pdsp::vec2<T>::type *pre,
+            const typename pdsp::vec2<T>::type *post, const typename pdsp::vec2<T>::type *bt,
+            const typename pdsp::vec2<T>::type *tw, hipStream_t s);
 
 }  // namespace pdsp_host

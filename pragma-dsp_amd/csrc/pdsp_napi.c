@@ -746,6 +746,34 @@ static napi_value Dft(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* czt(bins, step, start, radius, re, im, outRe, outIm): bins points of the chirp-z transform of one row of re.length
+ * samples (include/pdsp_hip.h: step and start in turns); im null or undefined means a real row.  The numbers are read
+ * first and the typed-array pointers last, as in dct().  Sizes the library refuses reach it unchanged (it fails before
+ * touching the outputs), so its message is what the caller sees. */
+static napi_value Czt(napi_env env, napi_callback_info info) {
+  napi_value argv[8];
+  if (!get_args(env, info, 8, argv)) return NULL;
+  int64_t bins;
+  double step, start, radius, *re, *im, *ore, *oim;
+  size_t nre, nim, nore, noim;
+  if (!get_i64(env, argv[0], &bins) || !get_f64(env, argv[1], &step) || !get_f64(env, argv[2], &start) ||
+      !get_f64(env, argv[3], &radius) || !f64_array(env, argv[4], &re, &nre) || !f64_array(env, argv[5], &im, &nim) ||
+      !f64_array(env, argv[6], &ore, &nore) || !f64_array(env, argv[7], &oim, &noim))
+    return NULL;
+  if (im && nim != nre) {
+    napi_throw_error(env, NULL, "pdsp_napi: czt real and imag lengths differ");
+    return NULL;
+  }
+  if (nre >= 1 && bins >= 1 && nre <= 8192 && bins <= 8192 && (int64_t)nre + bins - 1 <= 8192 &&
+      ((int64_t)nore < bins || (int64_t)noim < bins)) {
+    napi_throw_error(env, NULL, "pdsp_napi: czt output too small");
+    return NULL;
+  }
+  if (pdsp_czt_host_f64(re, im, 1, (long long)nre, (long long)bins, step, start, radius, ore, oim) != PDSP_OK)
+    return throw_pdsp(env);
+  return NULL;
+}
+
 /* dwt(mode, name, taps, levels, x, y): mode 0 = wavedec, 1 = waverec of one row of x.length values into y, with the
  * built-in wavelet `name` (a string) or, name null, the caller's taps; mode 2 = the taps of `name` into y, returning
  * their number (y of length 0 asks for the number alone).  The scalars are read first and the typed-array pointers
@@ -810,7 +838,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"firFilter", FirFilter},   {"resamplePoly", ResamplePoly}, {"upfirdn", Upfirdn},
       {"resampleDesign", ResampleDesign},   {"stft", Stft},               {"istft", Istft},
       {"dct", Dct},                 {"hilbert", Hilbert},         {"dft", Dft},
-      {"dwt", Dwt},
+      {"dwt", Dwt},                 {"czt", Czt},
   };
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
     napi_value f;

@@ -8,6 +8,7 @@ import * as dctNs from './dct';
 import * as hilbertNs from './hilbert';
 import * as dftNs from './dft';
 import * as waveletNs from './wavelet';
+import * as cztNs from './czt';
 
 export { spectrum, spectrumBatch, spectrumStream, SpectrumOptions, SpectrumPeak, SpectrumResult } from './spectrum';
 export { ComplexArray } from './core';
@@ -17,6 +18,7 @@ export { StftWindow, StftOptions, StftResult } from './stft';
 export { DctType, DctNorm, DctOptions } from './dct';
 export { HilbertOptions, AnalyticSignal } from './hilbert';
 export { DftResult } from './dft';
+export { CztInput, CztOptions, ZoomFftOptions, CztResult } from './czt';
 
 export const core: {
   createComplexArray: typeof coreNs.createComplexArray;
@@ -61,4 +63,8 @@ export const wavelet: {
   wavedec: typeof waveletNs.wavedec;
   waverec: typeof waveletNs.waverec;
   waveletTaps: typeof waveletNs.waveletTaps;
+};
+export const czt: {
+  czt: typeof cztNs.czt;
+  zoomFft: typeof cztNs.zoomFft;
 };

@@ -9,6 +9,7 @@
 //   require('.../js').hilbert    -> the Hilbert / analytic signal helpers (ROADMAP.md, v0.3)
 //   require('.../js').dft        -> the DFT of any length 2 ... 4096 (an extension: the reference has powers of two only)
 //   require('.../js').wavelet    -> the multi-level wavelet transform (ROADMAP.md, "E) Wavelets")
+//   require('.../js').czt        -> the chirp-z transform and zoom FFT (an extension: scipy.signal.czt / zoom_fft)
 const core = require('./core');
 const fourier = require('./fourier');
 const s = require('./spectrum');
@@ -19,6 +20,7 @@ const hilbert = require('./hilbert');
 const resample = require('./resample');
 const dft = require('./dft');
 const wavelet = require('./wavelet');
+const czt = require('./czt');
 
 module.exports = {
   spectrum: s.spectrum,
@@ -75,5 +77,10 @@ Object.defineProperty(module.exports, 'dft', {
 // Wavelets: planned by the reference (ROADMAP.md, item E), not enumerated for the same reason.
 Object.defineProperty(module.exports, 'wavelet', {
   value: { wavedec: wavelet.wavedec, waverec: wavelet.waverec, waveletTaps: wavelet.waveletTaps },
+  enumerable: false,
+});
+// Chirp-z transform and zoom FFT: an extension beside the any-length DFT, not enumerated for the same reason.
+Object.defineProperty(module.exports, 'czt', {
+  value: { czt: czt.czt, zoomFft: czt.zoomFft },
   enumerable: false,
 });
