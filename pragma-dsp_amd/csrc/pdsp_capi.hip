@@ -2255,69 +2255,62 @@ int pdsp_upfirdn_host_f64(const double *h, long long ntaps, const double *x, lon
   return resample_host(rs, x, batch, len, 1, y);
 }
 
-/* ---- any-length DFT: Bluestein's chirp-z algorithm ----------------------------- */
-
-// A DFT of L points is its two tables: the chirp c[n] = exp(-i pi (n^2 mod 2L) / L) and Bt = FFT_M(b) / M of the
-// chirp filter b[j] = conj c[|j|], both evaluated in f64 on the host and rounded once per precision, plus the radix
-// table of the M-point transform (the tw_half of a plan of 2M points).  They go up at create time through the plans'
-// uploader into the object's own lists.
-struct pdsp_dft {
-  int device = -1;
-  long long length = 0, m = 0;
-  int log2m = 0;
-  Tables<float> t32;   // tw_half: the M-point radix table; owned: every allocation of this precision
-  Tables<double> t64;
-  float2 *c32 = nullptr, *bt32 = nullptr;
-  double2 *c64 = nullptr, *bt64 = nullptr;
-};
+/* ---- chirp-z rows: the chirp-z transform, the zoom FFT and the any-length DFT ---- */
 
 namespace pdsp_host {
 
-constexpr long long kDftMinLength = 2, kDftMaxLength = 4096;
+// A chirp-z transform of L samples into K bins is its three tables -- pre[n] = a^-n w^(n^2/2), post[k] = w^(k^2/2) and
+// Bt = FFT_M(b) / M of the chirp filter b[j] = w^(-j^2/2) -- evaluated on the host and rounded once per precision, plus
+// the radix table of the M-point transform (the tw_half of a plan of 2M points).  They go up at create time through the
+// plans' uploader into the object's own lists.  A DFT is the transform with K = L whose post is its pre, the chirp
+// c[n] = exp(-i pi n^2 / L), uploaded once.
+template <typename T>
+struct ChirpSet {
+  Tables<T> t;  // tw_half: the M-point radix table; owned: every allocation of this precision
+  typename pdsp::vec2<T>::type *pre = nullptr, *post = nullptr, *bt = nullptr;
+};
+struct ChirpTables {
+  int device = -1;
+  long long length = 0, bins = 0, m = 0;
+  int log2m = 0;
+  ChirpSet<float> s32;
+  ChirpSet<double> s64;
+  template <typename T>
+  const ChirpSet<T> &set() const {
+    if constexpr (sizeof(T) == 4) return s32;
+    else return s64;
+  }
+};
 
-int check_dft_length(long long length) {
-  if (length < kDftMinLength || length > kDftMaxLength)
-    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "DFT length must be %lld ... %lld, got %lld", kDftMinLength, kDftMaxLength,
-                length);
-  return PDSP_OK;
-}
+}  // namespace pdsp_host
 
-// M = max(32, the smallest power of two >= 2L - 1): the circular convolution must hold the 2L - 1 lags of the chirp
-// filter; 32 is the smallest row of the sixteen-points-per-thread layout
-int dft_log2m(long long length) {
-  const int l = ilog2ll(2 * length - 1);
+struct pdsp_dft : pdsp_host::ChirpTables {};
+struct pdsp_czt : pdsp_host::ChirpTables {};
+
+namespace pdsp_host {
+
+constexpr long long kDftMinLength = 2, kDftMaxLength = 4096, kCztMaxConv = 8192;
+constexpr long double kPiL = 3.141592653589793238462643383279502884L;
+
+// M = max(32, the smallest power of two >= L + K - 1; the DFT's K is L): the circular convolution must hold the
+// L + K - 1 lags -(L - 1) ... K - 1 of the chirp filter; 32 is the smallest row of the sixteen-points-per-thread layout
+int chirp_log2m(long long length, long long bins) {
+  const int l = ilog2ll(length + bins - 1);
   return l < 5 ? 5 : l;
 }
 
-// c[n], n < L, in f64: the angle's numerator n^2 is reduced mod 2L in integers, so the argument of cos / sin stays
-// below 2 pi and carries no rounding of n^2
-std::vector<double2> dft_chirp(long long length) {
-  std::vector<double2> c((size_t)length);
-  for (long long n = 0; n < length; ++n) {
-    const double a = -M_PI * (double)((n * n) % (2 * length)) / (double)length;
-    c[(size_t)n] = double2{std::cos(a), std::sin(a)};
-  }
-  return c;
-}
-
-// Bt = FFT_M(b) / M, b[j] = conj c[|j|] at j and M - j for |j| < L, else 0.  Radix-2 decimation in time in long
-// double, every twiddle evaluated directly (no recurrence): built once per object, M <= 8192.
-std::vector<double2> dft_filter_spectrum(const std::vector<double2> &c, int log2m) {
-  const size_t m = (size_t)1 << log2m, len = c.size();
-  std::vector<long double> re(m, 0.0L), im(m, 0.0L);
-  auto rev = [&](size_t i) {
+// FFT_M(re + i im) / M, rounded to f64.  Radix-2 decimation in time in long double, every twiddle evaluated directly
+// (no recurrence): built once per object, M <= 8192.
+std::vector<double2> chirp_fft_over_m(std::vector<long double> re, std::vector<long double> im, int log2m) {
+  const size_t m = (size_t)1 << log2m;
+  for (size_t i = 0; i < m; ++i) {
     size_t r = 0;
     for (int b = 0; b < log2m; ++b) r |= ((i >> b) & 1) << (log2m - 1 - b);
-    return r;
-  };
-  for (size_t j = 0; j < len; ++j) {
-    re[rev(j)] = c[j].x, im[rev(j)] = -c[j].y;
-    if (j) re[rev(m - j)] = c[j].x, im[rev(m - j)] = -c[j].y;
+    if (i < r) std::swap(re[i], re[r]), std::swap(im[i], im[r]);
   }
-  const long double pi = 3.141592653589793238462643383279502884L;
   for (size_t half = 1; half < m; half <<= 1) {
     for (size_t k = 0; k < half; ++k) {
-      const long double a = -pi * (long double)k / (long double)half;
+      const long double a = -kPiL * (long double)k / (long double)half;
       const long double wr = cosl(a), wi = sinl(a);
       for (size_t i = k; i < m; i += 2 * half) {
         const size_t j = i + half;
@@ -2333,68 +2326,29 @@ std::vector<double2> dft_filter_spectrum(const std::vector<double2> &c, int log2
 }
 
 template <typename T2>
-std::vector<T2> dft_round(const std::vector<double2> &v) {
+std::vector<T2> chirp_round(const std::vector<double2> &v) {
   std::vector<T2> r(v.size());
   for (size_t i = 0; i < v.size(); ++i) r[i].x = (decltype(r[i].x))v[i].x, r[i].y = (decltype(r[i].y))v[i].y;
   return r;
 }
 
-template <typename T>
-hipError_t dft_upload(Tables<T> &t, int log2m, const std::vector<double2> &c, const std::vector<double2> &bt,
-                      typename pdsp::vec2<T>::type **c_out, typename pdsp::vec2<T>::type **bt_out) {
-  using T2 = typename pdsp::vec2<T>::type;
-  if (hipError_t e = upload_table(t, build_twiddles<T2>(log2m, pdsp::packed_log2e(log2m)), &t.tw_half)) return e;
-  if (hipError_t e = upload_table(t, dft_round<T2>(c), c_out)) return e;
-  return upload_table(t, dft_round<T2>(bt), bt_out);
+template <class H>
+int chirp_destroy(H *h) {
+  if (!h) return PDSP_OK;
+  {
+    DeviceGuard g(h->device);
+    h->s32.t.release();
+    h->s64.t.release();
+  }
+  delete h;
+  return PDSP_OK;
 }
 
-template <typename T> struct DftView {
-  const Tables<T> &t;
-  const typename pdsp::vec2<T>::type *c, *bt;
-};
-template <typename T> DftView<T> dft_view(const pdsp_dft *d);
-template <> DftView<float> dft_view<float>(const pdsp_dft *d) { return {d->t32, d->c32, d->bt32}; }
-template <> DftView<double> dft_view<double>(const pdsp_dft *d) { return {d->t64, d->c64, d->bt64}; }
-
-template <typename T>
-int dft_t(const pdsp_dft *d, long long batch, const T *re_in, const T *im_in, long long in_stride, T *re_out, T *im_out,
-          long long out_stride, int inverse, hipStream_t s) {
-  if (!d) return fail(PDSP_ERR_BAD_ARG, "dft is null");
-  const long long n = d->length;
-  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
-  if (in_stride < n || out_stride < n)
-    return fail(PDSP_ERR_BAD_ARG, "strides must be >= L = %lld, got in_stride %lld, out_stride %lld", n, in_stride,
-                out_stride);
-  long long ic = 0, oc = 0;
-  if (!mad_ok(batch - 1, in_stride, n, &ic) || !mad_ok(batch - 1, out_stride, n, &oc) || ic > (LLONG_MAX / 8) ||
-      oc > (LLONG_MAX / 8))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
-  if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
-  if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
-  // exact in place is safe (a row is loaded in full by its own workgroup before that workgroup's first barrier, and a
-  // thread stores only the m it loaded); any other overlap would let one row's stores reach another row's loads, or
-  // one plane's stores the other plane's loads of the same row
-  const size_t ib = (size_t)ic * sizeof(T), ob = (size_t)oc * sizeof(T);
-  const bool in_place = im_in && (const void *)re_out == (const void *)re_in &&
-                        (const void *)im_out == (const void *)im_in && in_stride == out_stride;
-  if (!in_place && (host_ranges_overlap(re_out, ob, re_in, ib) || host_ranges_overlap(re_out, ob, im_in, ib) ||
-                    host_ranges_overlap(im_out, ob, re_in, ib) || host_ranges_overlap(im_out, ob, im_in, ib)))
-    return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only re_out == re_in, im_out == im_in with equal strides "
-                                  "may share bytes)");
-  if (host_ranges_overlap(re_out, ob, im_out, ob))
-    return fail(PDSP_ERR_BAD_ARG, "the output planes overlap each other");
-  const DftView<T> v = dft_view<T>(d);
-  DeviceGuard dg(d->device);
-  PDSP_HIP_TRY(dg.err);
-  return dft_dev<T>(d->log2m, n, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, v.c, v.bt, v.t.tw_half,
-                    inverse != 0, s);
-}
-
-}  // namespace pdsp_host
-
-int pdsp_dft_create(long long length, int device, pdsp_dft **out) {
-  if (!out) return fail(PDSP_ERR_BAD_ARG, "out is null");
-  if (int rc = check_dft_length(length)) return rc;
+// The object of one transform on `device` (< 0: the current one), behind its creator's own argument checks: its
+// tables in both precisions.  post null: the DFT, whose post is its pre.  what: the transform's name in the message.
+template <class H>
+int chirp_create(H **out, const char *what, int device, long long length, long long bins,
+                 const std::vector<double2> &pre, const std::vector<double2> *post, const std::vector<double2> &bt) {
   if (int rc = require_device()) return rc;
   int count = 0;
   PDSP_HIP_TRY(hipGetDeviceCount(&count));
@@ -2402,94 +2356,146 @@ int pdsp_dft_create(long long length, int device, pdsp_dft **out) {
   if (device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", device, count);
   DeviceGuard g(device);
   PDSP_HIP_TRY(g.err);
-  pdsp_dft *d = new (std::nothrow) pdsp_dft();
-  if (!d) return fail(PDSP_ERR_BAD_ARG, "out of host memory");
-  d->device = device, d->length = length, d->log2m = dft_log2m(length), d->m = 1LL << d->log2m;
-  const std::vector<double2> c = dft_chirp(length), bt = dft_filter_spectrum(c, d->log2m);
-  hipError_t e = dft_upload<float>(d->t32, d->log2m, c, bt, &d->c32, &d->bt32);
-  if (e == hipSuccess) e = dft_upload<double>(d->t64, d->log2m, c, bt, &d->c64, &d->bt64);
+  H *h = new (std::nothrow) H();
+  if (!h) return fail(PDSP_ERR_BAD_ARG, "out of host memory");
+  h->device = device, h->length = length, h->bins = bins, h->log2m = chirp_log2m(length, bins), h->m = 1LL << h->log2m;
+  auto upload = [&](auto &s) -> hipError_t {
+    using T2 = std::remove_pointer_t<decltype(s.pre)>;
+    if (hipError_t e = upload_table(s.t, build_twiddles<T2>(h->log2m, pdsp::packed_log2e(h->log2m)), &s.t.tw_half))
+      return e;
+    if (hipError_t e = upload_table(s.t, chirp_round<T2>(pre), &s.pre)) return e;
+    if (!post) s.post = s.pre;
+    else if (hipError_t e = upload_table(s.t, chirp_round<T2>(*post), &s.post)) return e;
+    return upload_table(s.t, chirp_round<T2>(bt), &s.bt);
+  };
+  hipError_t e = upload(h->s32);
+  if (e == hipSuccess) e = upload(h->s64);
   if (e != hipSuccess) {
-    pdsp_dft_destroy(d);
-    return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the DFT tables", (int)e,
-                hipGetErrorString(e));
+    chirp_destroy(h);
+    return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the %s tables", (int)e,
+                hipGetErrorString(e), what);
   }
-  *out = d;
+  *out = h;
   return PDSP_OK;
 }
 
-int pdsp_dft_destroy(pdsp_dft *d) {
-  if (!d) return PDSP_OK;
-  {
-    DeviceGuard g(d->device);
-    d->t32.release();
-    d->t64.release();
-  }
-  delete d;
-  return PDSP_OK;
-}
-
-long long pdsp_dft_length(const pdsp_dft *d) { return d ? d->length : 0; }
-long long pdsp_dft_conv_size(const pdsp_dft *d) { return d ? d->m : 0; }
-
-int pdsp_dft_c2c_f32(const pdsp_dft *d, long long batch, const float *re_in, const float *im_in, long long in_stride,
-                     float *re_out, float *im_out, long long out_stride, int inverse, pdsp_stream stream) {
-  return dft_t<float>(d, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, inverse, (hipStream_t)stream);
-}
-int pdsp_dft_c2c_f64(const pdsp_dft *d, long long batch, const double *re_in, const double *im_in, long long in_stride,
-                     double *re_out, double *im_out, long long out_stride, int inverse, pdsp_stream stream) {
-  return dft_t<double>(d, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, inverse, (hipStream_t)stream);
-}
-
-// The host form rides the packed features' scaffold on the cached plan of 2M points (64 ... 16384: its stream, its
-// lock, its device); the DFT's own tables live for the call.  Buffer: out re | out im | in re | in im.
-int pdsp_dft_host_f64(const double *re_in, const double *im_in, long long batch, long long length, int inverse,
-                      double *re_out, double *im_out) {
-  if (int rc = check_dft_length(length)) return rc;
+// The row arguments of one launch, then the launch.  dft: 0 the chirp-z transform (czt_dev), +1 / -1 the forward /
+// inverse DFT (dft_dev).  Exact in place is safe: a workgroup loads all of its rows in full before its first barrier and stores
+// only into those rows, and with equal strides >= max(L, K) a row's samples and its bins share one slot that no other
+// row touches.  Any other overlap would let one row's stores reach another row's loads, or one plane's stores the other
+// plane's loads of the same row.  The two transforms keep their own in-place rules.  The chirp-z transform takes a real
+// row in place as well, its im_out apart, and compares the two planes over the larger of the two extents: the samples
+// of the last row may reach past its bins.  The DFT takes complex rows only: a real row has no in-place form, and with
+// K = L the output-plane check is the whole comparison.
+template <typename T>
+int chirp_t(const ChirpTables &c, int dft, long long batch, const T *re_in, const T *im_in, long long in_stride,
+            T *re_out, T *im_out, long long out_stride, hipStream_t s) {
+  const long long n = c.length, k = c.bins;
   if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
-  long long count = 0;
-  if (batch > 0x7fffffffLL || !mad_ok(batch, length, 0, &count) || count > (1LL << 40))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x %lld overflows", batch, length);
+  if (in_stride < n || out_stride < k)
+    return fail(PDSP_ERR_BAD_ARG, "strides must be >= L = %lld in and >= K = %lld out, got in_stride %lld, out_stride %lld",
+                n, k, in_stride, out_stride);
+  long long ic = 0, oc = 0;
+  if (!mad_ok(batch - 1, in_stride, n, &ic) || !mad_ok(batch - 1, out_stride, k, &oc) || ic > (LLONG_MAX / 8) ||
+      oc > (LLONG_MAX / 8))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
   if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
-  const size_t nx = (size_t)count;
+  const size_t ib = (size_t)ic * sizeof(T), ob = (size_t)oc * sizeof(T), xb = ib > ob ? ib : ob;
+  const bool in_place = (const void *)re_out == (const void *)re_in && in_stride == out_stride &&
+                        (im_in ? (const void *)im_out == (const void *)im_in : !dft);
+  const bool clash = !in_place ? (host_ranges_overlap(re_out, ob, re_in, ib) || host_ranges_overlap(re_out, ob, im_in, ib) ||
+                                  host_ranges_overlap(im_out, ob, re_in, ib) || host_ranges_overlap(im_out, ob, im_in, ib))
+                     : dft     ? false
+                     : im_in   ? host_ranges_overlap(re_in, xb, im_in, xb)
+                               : host_ranges_overlap(im_out, ob, re_in, xb);
+  if (clash)
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only re_out == re_in, im_out == im_in%s with equal strides "
+                                  "may share bytes)", dft ? "" : " -- a real row's im_out apart --");
+  if (host_ranges_overlap(re_out, ob, im_out, ob))
+    return fail(PDSP_ERR_BAD_ARG, "the output planes overlap each other");
+  const ChirpSet<T> &v = c.set<T>();
+  DeviceGuard dg(c.device);
+  PDSP_HIP_TRY(dg.err);
+  if (dft)
+    return dft_dev<T>(c.log2m, n, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, v.pre, v.bt, v.t.tw_half,
+                      dft < 0, s);
+  return czt_dev<T>(c.log2m, n, k, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, v.pre, v.post, v.bt,
+                    v.t.tw_half, s);
+}
+
+// The host forms ride the packed features' scaffold on the cached plan of 2M points (64 ... 16384: its stream, its
+// lock, its device), behind their own size checks; the transform's own tables live for the call: create(device, &h).
+// Buffer: out re | out im | in re | in im.
+template <class H, class Create>
+int chirp_host(int dft, const double *re_in, const double *im_in, long long batch, long long length, long long bins,
+               double *re_out, double *im_out, Create create) {
+  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
+  long long cin = 0, cout = 0;
+  if (batch > 0x7fffffffLL || !mad_ok(batch, length, 0, &cin) || !mad_ok(batch, bins, 0, &cout) || cin > (1LL << 40) ||
+      cout > (1LL << 40))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x (%lld, %lld) overflows", batch, length, bins);
+  if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  const size_t nx = (size_t)cin, ny = (size_t)cout;
   struct Owner {
-    pdsp_dft *p = nullptr;
-    ~Owner() { pdsp_dft_destroy(p); }
+    H *p = nullptr;
+    ~Owner() { chirp_destroy(p); }
   } own;
   return packed_host_call(
-      2LL << dft_log2m(length), PDSP_WIN_RECT, 4 * nx,
+      2LL << chirp_log2m(length, bins), PDSP_WIN_RECT, 2 * ny + 2 * nx,
       [&](pdsp_plan *plan, hipStream_t s, const double *, double *d) -> int {
-        if (int rc = pdsp_dft_create(length, plan->device, &own.p)) return rc;
-        PDSP_HIP_TRY(hipMemcpyAsync(d + 2 * nx, re_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
-        if (im_in) PDSP_HIP_TRY(hipMemcpyAsync(d + 3 * nx, im_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
-        return dft_t<double>(own.p, batch, d + 2 * nx, im_in ? d + 3 * nx : nullptr, length, d, d + nx, length, inverse,
-                             s);
+        if (int rc = create(plan->device, &own.p)) return rc;
+        double *const xr = d + 2 * ny, *const xi = xr + nx;
+        PDSP_HIP_TRY(hipMemcpyAsync(xr, re_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
+        if (im_in) PDSP_HIP_TRY(hipMemcpyAsync(xi, im_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
+        return chirp_t<double>(*own.p, dft, batch, xr, im_in ? xi : nullptr, length, d, d + ny, bins, s);
       },
       [&](const double *d) -> int {
-        PDSP_HIP_TRY(hipMemcpy(re_out, d, nx * sizeof(double), hipMemcpyDeviceToHost));
-        PDSP_HIP_TRY(hipMemcpy(im_out, d + nx, nx * sizeof(double), hipMemcpyDeviceToHost));
+        PDSP_HIP_TRY(hipMemcpy(re_out, d, ny * sizeof(double), hipMemcpyDeviceToHost));
+        PDSP_HIP_TRY(hipMemcpy(im_out, d + ny, ny * sizeof(double), hipMemcpyDeviceToHost));
         return PDSP_OK;
       });
 }
 
-/* ---- chirp-z transform and zoom FFT --------------------------------------------- */
+/* the any-length DFT: Bluestein's algorithm */
 
-// A chirp-z transform is its three tables -- pre[n] = a^-n w^(n^2/2), post[k] = w^(k^2/2) and Bt = FFT_M(b) / M of the
-// chirp filter b[j] = w^(-j^2/2) -- evaluated in long double on the host from exactly reduced phases and rounded once
-// per precision, plus the radix table of the M-point transform (the tw_half of a plan of 2M points).  They go up at
-// create time through the plans' uploader into the object's own lists.
-struct pdsp_czt {
-  int device = -1;
-  long long length = 0, bins = 0, m = 0;
-  int log2m = 0;
-  Tables<float> t32;   // tw_half: the M-point radix table; owned: every allocation of this precision
-  Tables<double> t64;
-  float2 *pre32 = nullptr, *post32 = nullptr, *bt32 = nullptr;
-  double2 *pre64 = nullptr, *post64 = nullptr, *bt64 = nullptr;
-};
+int check_dft_length(long long length) {
+  if (length < kDftMinLength || length > kDftMaxLength)
+    return fail(PDSP_ERR_UNSUPPORTED_SIZE, "DFT length must be %lld ... %lld, got %lld", kDftMinLength, kDftMaxLength,
+                length);
+  return PDSP_OK;
+}
 
-namespace pdsp_host {
+// c[n] = exp(-i pi n^2 / L), n < L, in f64: the angle's numerator n^2 is reduced mod 2L in integers, so the argument of
+// cos / sin stays below 2 pi and carries no rounding of n^2
+std::vector<double2> dft_chirp(long long length) {
+  std::vector<double2> c((size_t)length);
+  for (long long n = 0; n < length; ++n) {
+    const double a = -M_PI * (double)((n * n) % (2 * length)) / (double)length;
+    c[(size_t)n] = double2{std::cos(a), std::sin(a)};
+  }
+  return c;
+}
 
-constexpr long long kCztMaxConv = 8192;
+// Bt of the even filter b[j] = conj c[|j|] at j and M - j for |j| < L, else 0
+std::vector<double2> dft_filter_spectrum(const std::vector<double2> &c, int log2m) {
+  const size_t m = (size_t)1 << log2m;
+  std::vector<long double> re(m, 0.0L), im(m, 0.0L);
+  for (size_t j = 0; j < c.size(); ++j) {
+    re[j] = c[j].x, im[j] = -c[j].y;
+    if (j) re[m - j] = c[j].x, im[m - j] = -c[j].y;
+  }
+  return chirp_fft_over_m(std::move(re), std::move(im), log2m);
+}
+
+template <typename T>
+int dft_t(const pdsp_dft *d, long long batch, const T *re_in, const T *im_in, long long in_stride, T *re_out, T *im_out,
+          long long out_stride, int inverse, hipStream_t s) {
+  if (!d) return fail(PDSP_ERR_BAD_ARG, "dft is null");
+  return chirp_t<T>(*d, inverse ? -1 : 1, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, s);
+}
+
+/* the chirp-z transform and zoom FFT */
 
 int check_czt_args(long long length, long long bins, double step, double start, double radius) {
   if (length < 1) return fail(PDSP_ERR_UNSUPPORTED_SIZE, "CZT length must be >= 1, got %lld", length);
@@ -2509,16 +2515,9 @@ int check_czt_args(long long length, long long bins, double step, double start, 
   return PDSP_OK;
 }
 
-// M = max(32, the smallest power of two >= L + K - 1): the circular convolution must hold the L + K - 1 lags
-// -(L - 1) ... K - 1 of the chirp filter; 32 is the smallest row of the sixteen-points-per-thread layout
-int czt_log2m(long long length, long long bins) {
-  const int l = ilog2ll(length + bins - 1);
-  return l < 5 ? 5 : l;
-}
-
-// (n t) mod `mod` in turns, exactly: n an integer below 2^27 (or its square), t the caller's double.  p + e is the
-// product without error; fmod of p is exact; the error term is added after the reduction, so the sum carries the
-// product's low bits however large n t is.
+// The tables are evaluated in long double from exactly reduced phases.  (n t) mod `mod` in turns, exactly: n an integer
+// below 2^27 (or its square), t the caller's double.  p + e is the product without error; fmod of p is exact; the error
+// term is added after the reduction, so the sum carries the product's low bits however large n t is.
 long double czt_turns(long long n, double t, double mod) {
   const double p = (double)n * t, e = std::fma((double)n, t, -p);
   return (long double)std::fmod(p, mod) + (long double)e;
@@ -2527,7 +2526,6 @@ long double czt_turns(long long n, double t, double mod) {
 struct ldcx {
   long double x, y;
 };
-constexpr long double kPiL = 3.141592653589793238462643383279502884L;
 
 // w^(sgn n^2 / 2), w = exp(-2 pi i step): the half-turn chirp, n^2 step reduced mod 2
 ldcx czt_chirp(long long n, double step, int sgn) {
@@ -2559,132 +2557,66 @@ std::vector<double2> czt_post(long long bins, double step) {
   return czt_table(bins, [&](long long k) { return czt_chirp(k, step, 1); });
 }
 
-// Bt = FFT_M(b) / M, b[j] = w^(-j^2/2) at j for 0 <= j < K, at M + j for -(L - 1) <= j < 0, else 0 (M >= L + K - 1:
-// the two runs do not meet).  b's support is not symmetric, so this is not dft_filter_spectrum's even filter; the
-// transform is the same: radix-2 decimation in time in long double, every twiddle evaluated directly.
+// Bt of b[j] = w^(-j^2/2) at j for 0 <= j < K, at M + j for -(L - 1) <= j < 0, else 0 (M >= L + K - 1: the two runs do
+// not meet).  b's support is not symmetric: this is not the DFT's even filter.
 std::vector<double2> czt_filter_spectrum(long long length, long long bins, double step, int log2m) {
   const size_t m = (size_t)1 << log2m;
   std::vector<long double> re(m, 0.0L), im(m, 0.0L);
-  auto rev = [&](size_t i) {
-    size_t r = 0;
-    for (int b = 0; b < log2m; ++b) r |= ((i >> b) & 1) << (log2m - 1 - b);
-    return r;
-  };
   for (long long j = -(length - 1); j < bins; ++j) {
     const ldcx v = czt_chirp(j, step, -1);
-    const size_t at = rev((size_t)(j < 0 ? (long long)m + j : j));
+    const size_t at = (size_t)(j < 0 ? (long long)m + j : j);
     re[at] = v.x, im[at] = v.y;
   }
-  for (size_t half = 1; half < m; half <<= 1) {
-    for (size_t k = 0; k < half; ++k) {
-      const long double a = -kPiL * (long double)k / (long double)half;
-      const long double wr = cosl(a), wi = sinl(a);
-      for (size_t i = k; i < m; i += 2 * half) {
-        const size_t j = i + half;
-        const long double tr = re[j] * wr - im[j] * wi, ti = re[j] * wi + im[j] * wr;
-        re[j] = re[i] - tr, im[j] = im[i] - ti;
-        re[i] += tr, im[i] += ti;
-      }
-    }
-  }
-  std::vector<double2> bt(m);
-  for (size_t k = 0; k < m; ++k) bt[k] = double2{(double)(re[k] / (long double)m), (double)(im[k] / (long double)m)};
-  return bt;
+  return chirp_fft_over_m(std::move(re), std::move(im), log2m);
 }
-
-template <typename T> struct CztView {
-  const Tables<T> &t;
-  const typename pdsp::vec2<T>::type *pre, *post, *bt;
-};
-template <typename T> CztView<T> czt_view(const pdsp_czt *c);
-template <> CztView<float> czt_view<float>(const pdsp_czt *c) { return {c->t32, c->pre32, c->post32, c->bt32}; }
-template <> CztView<double> czt_view<double>(const pdsp_czt *c) { return {c->t64, c->pre64, c->post64, c->bt64}; }
 
 template <typename T>
 int czt_t(const pdsp_czt *c, long long batch, const T *re_in, const T *im_in, long long in_stride, T *re_out, T *im_out,
           long long out_stride, hipStream_t s) {
   if (!c) return fail(PDSP_ERR_BAD_ARG, "czt is null");
-  const long long n = c->length, k = c->bins;
-  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
-  if (in_stride < n || out_stride < k)
-    return fail(PDSP_ERR_BAD_ARG, "strides must be >= L = %lld in and >= K = %lld out, got in_stride %lld, out_stride %lld",
-                n, k, in_stride, out_stride);
-  long long ic = 0, oc = 0;
-  if (!mad_ok(batch - 1, in_stride, n, &ic) || !mad_ok(batch - 1, out_stride, k, &oc) || ic > (LLONG_MAX / 8) ||
-      oc > (LLONG_MAX / 8))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
-  if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
-  if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
-  // Exact in place is safe: a workgroup loads all of its rows in full before its first barrier and stores only into
-  // those rows, and with equal strides >= max(L, K) a row's samples and its bins share one slot that no other row
-  // touches.  Any other overlap would let one row's stores reach another row's loads, or one plane's stores the
-  // other plane's loads of the same row.  In place the two planes are compared over the larger of the two extents: the
-  // samples of the last row may reach past its bins.
-  const size_t ib = (size_t)ic * sizeof(T), ob = (size_t)oc * sizeof(T), xb = ib > ob ? ib : ob;
-  const bool in_place = (const void *)re_out == (const void *)re_in && in_stride == out_stride &&
-                        (!im_in || (const void *)im_out == (const void *)im_in);
-  const bool clash = in_place ? (im_in ? host_ranges_overlap(re_in, xb, im_in, xb) : host_ranges_overlap(im_out, ob, re_in, xb))
-                              : (host_ranges_overlap(re_out, ob, re_in, ib) || host_ranges_overlap(re_out, ob, im_in, ib) ||
-                                 host_ranges_overlap(im_out, ob, re_in, ib) || host_ranges_overlap(im_out, ob, im_in, ib));
-  if (clash)
-    return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only re_out == re_in, im_out == im_in -- a real row's im_out "
-                                  "apart -- with equal strides may share bytes)");
-  if (host_ranges_overlap(re_out, ob, im_out, ob))
-    return fail(PDSP_ERR_BAD_ARG, "the output planes overlap each other");
-  const CztView<T> v = czt_view<T>(c);
-  DeviceGuard dg(c->device);
-  PDSP_HIP_TRY(dg.err);
-  return czt_dev<T>(c->log2m, n, k, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, v.pre, v.post, v.bt,
-                    v.t.tw_half, s);
+  return chirp_t<T>(*c, 0, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, s);
 }
 
 }  // namespace pdsp_host
+
+int pdsp_dft_create(long long length, int device, pdsp_dft **out) {
+  if (!out) return fail(PDSP_ERR_BAD_ARG, "out is null");
+  if (int rc = check_dft_length(length)) return rc;
+  const std::vector<double2> c = dft_chirp(length);
+  return chirp_create(out, "DFT", device, length, length, c, nullptr,
+                      dft_filter_spectrum(c, chirp_log2m(length, length)));
+}
+
+int pdsp_dft_destroy(pdsp_dft *d) { return chirp_destroy(d); }
+long long pdsp_dft_length(const pdsp_dft *d) { return d ? d->length : 0; }
+long long pdsp_dft_conv_size(const pdsp_dft *d) { return d ? d->m : 0; }
+
+int pdsp_dft_c2c_f32(const pdsp_dft *d, long long batch, const float *re_in, const float *im_in, long long in_stride,
+                     float *re_out, float *im_out, long long out_stride, int inverse, pdsp_stream stream) {
+  return dft_t<float>(d, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, inverse, (hipStream_t)stream);
+}
+int pdsp_dft_c2c_f64(const pdsp_dft *d, long long batch, const double *re_in, const double *im_in, long long in_stride,
+                     double *re_out, double *im_out, long long out_stride, int inverse, pdsp_stream stream) {
+  return dft_t<double>(d, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, inverse, (hipStream_t)stream);
+}
+
+int pdsp_dft_host_f64(const double *re_in, const double *im_in, long long batch, long long length, int inverse,
+                      double *re_out, double *im_out) {
+  if (int rc = check_dft_length(length)) return rc;
+  return chirp_host<pdsp_dft>(inverse ? -1 : 1, re_in, im_in, batch, length, length, re_out, im_out,
+                              [&](int device, pdsp_dft **d) { return pdsp_dft_create(length, device, d); });
+}
 
 int pdsp_czt_create(long long length, long long bins, double step, double start, double radius, int device,
                     pdsp_czt **out) {
   if (!out) return fail(PDSP_ERR_BAD_ARG, "out is null");
   if (int rc = check_czt_args(length, bins, step, start, radius)) return rc;
-  if (int rc = require_device()) return rc;
-  int count = 0;
-  PDSP_HIP_TRY(hipGetDeviceCount(&count));
-  if (device < 0) PDSP_HIP_TRY(hipGetDevice(&device));
-  if (device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", device, count);
-  DeviceGuard g(device);
-  PDSP_HIP_TRY(g.err);
-  pdsp_czt *c = new (std::nothrow) pdsp_czt();
-  if (!c) return fail(PDSP_ERR_BAD_ARG, "out of host memory");
-  c->device = device, c->length = length, c->bins = bins, c->log2m = czt_log2m(length, bins), c->m = 1LL << c->log2m;
-  const std::vector<double2> pre = czt_pre(length, step, start, radius), post = czt_post(bins, step),
-                             bt = czt_filter_spectrum(length, bins, step, c->log2m);
-  auto upload = [&](auto &t, auto **pre_out, auto **post_out, auto **bt_out) -> hipError_t {
-    using T2 = std::remove_pointer_t<std::remove_pointer_t<decltype(pre_out)>>;
-    if (hipError_t e = upload_table(t, build_twiddles<T2>(c->log2m, pdsp::packed_log2e(c->log2m)), &t.tw_half)) return e;
-    if (hipError_t e = upload_table(t, dft_round<T2>(pre), pre_out)) return e;
-    if (hipError_t e = upload_table(t, dft_round<T2>(post), post_out)) return e;
-    return upload_table(t, dft_round<T2>(bt), bt_out);
-  };
-  hipError_t e = upload(c->t32, &c->pre32, &c->post32, &c->bt32);
-  if (e == hipSuccess) e = upload(c->t64, &c->pre64, &c->post64, &c->bt64);
-  if (e != hipSuccess) {
-    pdsp_czt_destroy(c);
-    return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the CZT tables", (int)e,
-                hipGetErrorString(e));
-  }
-  *out = c;
-  return PDSP_OK;
+  const std::vector<double2> post = czt_post(bins, step);
+  return chirp_create(out, "CZT", device, length, bins, czt_pre(length, step, start, radius), &post,
+                      czt_filter_spectrum(length, bins, step, chirp_log2m(length, bins)));
 }
 
-int pdsp_czt_destroy(pdsp_czt *c) {
-  if (!c) return PDSP_OK;
-  {
-    DeviceGuard g(c->device);
-    c->t32.release();
-    c->t64.release();
-  }
-  delete c;
-  return PDSP_OK;
-}
-
+int pdsp_czt_destroy(pdsp_czt *c) { return chirp_destroy(c); }
 long long pdsp_czt_length(const pdsp_czt *c) { return c ? c->length : 0; }
 long long pdsp_czt_bins(const pdsp_czt *c) { return c ? c->bins : 0; }
 long long pdsp_czt_conv_size(const pdsp_czt *c) { return c ? c->m : 0; }
@@ -2698,36 +2630,12 @@ int pdsp_czt_f64(const pdsp_czt *c, long long batch, const double *re_in, const 
   return czt_t<double>(c, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, (hipStream_t)stream);
 }
 
-// The host form rides the packed features' scaffold on the cached plan of 2M points, as pdsp_dft_host_f64 does; the
-// transform's own tables live for the call.  Buffer: out re | out im | in re | in im.
 int pdsp_czt_host_f64(const double *re_in, const double *im_in, long long batch, long long length, long long bins,
                       double step, double start, double radius, double *re_out, double *im_out) {
   if (int rc = check_czt_args(length, bins, step, start, radius)) return rc;
-  if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
-  long long cin = 0, cout = 0;
-  if (batch > 0x7fffffffLL || !mad_ok(batch, length, 0, &cin) || !mad_ok(batch, bins, 0, &cout) || cin > (1LL << 40) ||
-      cout > (1LL << 40))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x (%lld, %lld) overflows", batch, length, bins);
-  if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
-  const size_t nx = (size_t)cin, ny = (size_t)cout;
-  struct Owner {
-    pdsp_czt *p = nullptr;
-    ~Owner() { pdsp_czt_destroy(p); }
-  } own;
-  return packed_host_call(
-      2LL << czt_log2m(length, bins), PDSP_WIN_RECT, 2 * ny + 2 * nx,
-      [&](pdsp_plan *plan, hipStream_t s, const double *, double *d) -> int {
-        if (int rc = pdsp_czt_create(length, bins, step, start, radius, plan->device, &own.p)) return rc;
-        double *const xr = d + 2 * ny, *const xi = xr + nx;
-        PDSP_HIP_TRY(hipMemcpyAsync(xr, re_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
-        if (im_in) PDSP_HIP_TRY(hipMemcpyAsync(xi, im_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
-        return czt_t<double>(own.p, batch, xr, im_in ? xi : nullptr, length, d, d + ny, bins, s);
-      },
-      [&](const double *d) -> int {
-        PDSP_HIP_TRY(hipMemcpy(re_out, d, ny * sizeof(double), hipMemcpyDeviceToHost));
-        PDSP_HIP_TRY(hipMemcpy(im_out, d + ny, ny * sizeof(double), hipMemcpyDeviceToHost));
-        return PDSP_OK;
-      });
+  return chirp_host<pdsp_czt>(0, re_in, im_in, batch, length, bins, re_out, im_out, [&](int device, pdsp_czt **c) {
+    return pdsp_czt_create(length, bins, step, start, radius, device, c);
+  });
 }
 
 /* ---- multi-level wavelet transform: wavedec / waverec -------------------------- */

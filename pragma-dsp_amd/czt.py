@@ -18,24 +18,18 @@ torch is used for device memory and streams only; the arithmetic is the HIP kern
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import _capi
-from ._capi import PdspError, check, lib
-from .filters import _rows
+from ._capi import PdspError, lib
+from ._chirp import ChirpRows, host_call, host_planes
+from ._chirp import integer as _int
 
 MAX_CONV = 8192
 SPIRAL = "spirals are not supported: |w| must be 1 (an arc of a circle), got |w| = {!r}"
-
-
-def _int(v, name) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -2 ** 63 <= int(v) < 2 ** 63:
-        raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be an integer, got {v!r}")
-    return int(v)
 
 
 def _real(v, name) -> float:
@@ -87,21 +81,16 @@ def _zoom(fn, bins, fs, endpoint):
     return ((f2 - f1) / div if div else 0.0), f1 / fs
 
 
-class Czt:
+class Czt(ChirpRows):
     """A pdsp_czt on one GPU: the pre, post and chirp-filter tables of one transform, both precisions."""
+
+    _destroy = lib.pdsp_czt_destroy
+    _forward = (lib.pdsp_czt_f32, lib.pdsp_czt_f64)
 
     def __init__(self, length, bins, step, start=0.0, radius=1.0, device=None):
         length, bins = _int(length, "length"), _int(bins, "bins")
         step, start, radius = _real(step, "step"), _real(start, "start"), _real(radius, "radius")
-        self._h = C.c_void_p()
-        if not torch.cuda.is_available():
-            # argument errors come first, as everywhere: the library checks them without a device
-            check(lib.pdsp_czt_create(length, bins, step, start, radius, -1, C.byref(self._h)))
-            raise PdspError(_capi.ERR_DEVICE, "no HIP device available (the pdsp engine has no CPU fallback)")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        check(lib.pdsp_czt_create(length, bins, step, start, radius, self.device.index, C.byref(self._h)))
+        self._create(lib.pdsp_czt_create, device, length, bins, step, start, radius)
         self.length = int(lib.pdsp_czt_length(self._h))
         self.bins = int(lib.pdsp_czt_bins(self._h))
         self.conv_size = int(lib.pdsp_czt_conv_size(self._h))  # M, the points of the circular convolution
@@ -116,62 +105,19 @@ class Czt:
         step, start = _zoom(fn, bins, fs, endpoint)
         return cls(length, bins, step, start, 1.0, device)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            lib.pdsp_czt_destroy(h)
-            self._h = None
-
-    def _plane(self, t, name, width, like=None, shape=None):
-        if (not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.float64) or not t.is_cuda
-                or t.device != self.device or t.dim() == 0 or t.shape[-1] != width):
-            raise PdspError(_capi.ERR_BAD_ARG,
-                            f"{name} must be a float32 or float64 tensor [..., {width}] on {self.device}")
-        if like is not None and (t.dtype != like.dtype or tuple(t.shape) != tuple(shape)):
-            raise PdspError(_capi.ERR_BAD_ARG, f"{name} must have the dtype of re and the shape {tuple(shape)}")
-        return _rows(t, name)
-
     def forward(self, re: torch.Tensor, im: torch.Tensor | None = None, out=None):
         """Rows along the last axis ([..., L] contiguous, or a 2-D view with a row stride >= L) -> (re, im) of
         [..., K]; im None means real rows.  One launch on the current stream.  out: a pair of planes [..., K]; the
         exact in-place call out=(re, im) is taken where the row strides are equal."""
-        rows, stride = self._plane(re, "re", self.length)
-        if im is not None and self._plane(im, "im", self.length, re, re.shape) != (rows, stride):
-            raise PdspError(_capi.ERR_BAD_ARG, "re and im must have the same row stride")
-        oshape = tuple(re.shape[:-1]) + (self.bins,)
-        if out is None:
-            out = (torch.empty(oshape, dtype=re.dtype, device=self.device),
-                   torch.empty(oshape, dtype=re.dtype, device=self.device))
-        elif not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise PdspError(_capi.ERR_BAD_ARG, "out must be a pair of tensors (re, im)")
-        o_rows = [self._plane(o, "out", self.bins, re, oshape) for o in out]
-        if o_rows[0] != o_rows[1]:
-            raise PdspError(_capi.ERR_BAD_ARG, "the two out planes must have the same row stride")
-        with torch.cuda.device(self.device):
-            fn = lib.pdsp_czt_f32 if re.dtype == torch.float32 else lib.pdsp_czt_f64
-            check(fn(self._h, rows, C.c_void_p(re.data_ptr()), C.c_void_p(im.data_ptr()) if im is not None else None,
-                     stride, C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), o_rows[0][1],
-                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-        return out[0], out[1]
+        return self._run(re, im, out)
 
 
 def _host(x, bins, step, start, radius) -> np.ndarray:
-    a = np.asarray(x)
-    cplx = np.iscomplexobj(a)
-    a = np.asarray(a, dtype=np.complex128 if cplx else np.float64)
-    if a.ndim == 0:
-        raise PdspError(_capi.ERR_BAD_ARG, "x must have at least one axis")
+    a, re, im = host_planes(x)
     ln = a.shape[-1]
     bins = ln if bins is None else _int(bins, "m")
-    rows = int(np.prod(a.shape[:-1], dtype=np.int64))
-    re = np.ascontiguousarray(a.real).reshape(rows, ln)
-    im = np.ascontiguousarray(a.imag).reshape(rows, ln) if cplx else None
-    # sizes the library refuses get no buffers: the library fails before it writes
-    k = bins if ln >= 1 and bins >= 1 and ln + bins - 1 <= MAX_CONV else 0
-    ore, oim = np.empty((rows, k), dtype=np.float64), np.empty((rows, k), dtype=np.float64)
-    check(lib.pdsp_czt_host_f64(_capi.dptr(re), _capi.dptr(im), rows, ln, bins, step, start, radius, _capi.dptr(ore),
-                                _capi.dptr(oim)))
-    return (ore + 1j * oim).reshape(a.shape[:-1] + (bins,))
+    return host_call(lib.pdsp_czt_host_f64, a, re, im, bins, ln >= 1 and bins >= 1 and ln + bins - 1 <= MAX_CONV,
+                     bins, step, start, radius)
 
 
 def czt(x, m=None, w=None, a=1 + 0j) -> np.ndarray:
