@@ -92,6 +92,52 @@ PDSP_API int pdsp_dev_complex_op_vec4(int op, long long count, const float *a_re
                                       const float *b_re, const float *b_im, long long b_len, const float *out_re,
                                       const float *out_im, int *vec4);
 
+/* What a pdsp_fft_forward_real_* / _forward_complex_* / _inverse_* call (pdsp_dev_transform_path_*: the planes in that
+ * entry point's order, im_in null for real rows, inverse = 1 for pdsp_fft_inverse_*) or a pdsp_spectrum_* /
+ * pdsp_spectrum_peaks_f32 call (pdsp_dev_spectrum_path_*: peak_idx_out and peaks_out as the call has them, the other
+ * null) would run on these very pointers under the current switches.  The queries run the call's own argument checks
+ * -- a call that is refused is refused here with the same code and text -- and then the decision function the call
+ * itself switches on (pdsp_dispatch.inc: Pick), and write it to info.  They launch nothing and
+ * allocate nothing; the pointers are only looked at.  An empty batch gives path 0.  info, PDSP_DEV_PATH_INFO ints:
+ *   [0] path: 1 fft_tiny_staged_kernel, 2 fft_staged_kernel, 3 fft_stockham_kernel, 4 fft_split2_kernel,
+ *       5 fft_split4_kernel, 6 fft_real_kernel (f64 packed-real rows), 7 fft_paired_kernel, 8 two or three tile passes,
+ *       9 fused four-step (fourstep_cols_kernel, N2-point rows, fourstep_out_kernel), 10 general four-step
+ *       (bigfft_transpose_kernel around N1- and N2-point rows); spectra: 9 and 10 with amplitude rows from the last
+ *       pass, 11 memset (empty frames), 12 packed-real frames on tile passes + split_amp_rows_kernel,
+ *       13 spectrum_staged_kernel, 14 spectrum_dif16k_kernel, 15 spectrum_packed_kernel, 16 fft_tiny_staged_kernel
+ *       with amplitude store, 17 the complex kernel on (x, 0) with amplitude store (N < 64)
+ *   [1] rows: the rows kernel as a path value 3 ... 5 -- paths 3 ... 5: the path itself; 9 and 10: of the N2-point rows
+ *   [2] n1_rows: path 10, the kernel of the N1-point rows, 2 ... 5; [3] n1_square: 1 = N1 == N2, they run like the
+ *       N2-point rows on the same tables, 0 = on the N1-point tables of their own
+ *   [4] np: tile passes run (path 8; path 12 with head 0); [5..7] tile: each pass's kernel, 1 tile_pass_kernel,
+ *       2 tile_cols512_kernel, 3 tile_rows512_kernel; [8] tile_major: the planes between the first two of three passes
+ *       are tile-major, not in natural order
+ *   [9] pairs: scratch plane pairs drawn; [10] out_first: the output planes serve as the first intermediate pair
+ *       (paths 8 with three passes and 10, transforms only: output and input share no bytes)
+ *   [11] fast: paths 13 ... 15, whole pair-aligned one-sided frames without phase rows; [12] wmode: the same paths,
+ *       0 rect, 1 window table, 2 / 3 fused two- / three-term cosine sum
+ *   [13] first: path 12, the first pass's loader, 3 rect, 4 window table, 5 / 6 fused two- / three-term cosine sum
+ *   [14] fused_peaks: paths 14 and 15, the peak records are written by the spectrum kernel itself
+ *   [15] peaks: the kernels that run on the stored rows afterwards, bits 1 peak_wave_kernel, 2 find_peak_kernel,
+ *       4 peak_from_rows_kernel
+ *   [16] head: path 12, what runs the N/2-point transform: 0 the tile passes of [4..8], 1 fft_split4_kernel with the
+ *       packed loader, 2 fft_paired_kernel with the packed loader */
+#define PDSP_DEV_PATH_INFO 17
+PDSP_API int pdsp_dev_transform_path_f32(const pdsp_plan *plan, long long batch, const float *re_in, const float *im_in,
+                                         const float *re_out, const float *im_out, int inverse,
+                                         int info[PDSP_DEV_PATH_INFO]);
+PDSP_API int pdsp_dev_transform_path_f64(const pdsp_plan *plan, long long batch, const double *re_in,
+                                         const double *im_in, const double *re_out, const double *im_out, int inverse,
+                                         int info[PDSP_DEV_PATH_INFO]);
+PDSP_API int pdsp_dev_spectrum_path_f32(const pdsp_plan *plan, long long batch, const float *frames, long long frame_len,
+                                        long long frame_stride, const float *window, int sides, const float *amp_out,
+                                        const float *phase_out, const int32_t *peak_idx_out,
+                                        const pdsp_peak32 *peaks_out, double sample_rate, int info[PDSP_DEV_PATH_INFO]);
+PDSP_API int pdsp_dev_spectrum_path_f64(const pdsp_plan *plan, long long batch, const double *frames,
+                                        long long frame_len, long long frame_stride, const double *window, int sides,
+                                        const double *amp_out, const double *phase_out, const int32_t *peak_idx_out,
+                                        const pdsp_peak32 *peaks_out, double sample_rate, int info[PDSP_DEV_PATH_INFO]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,10 @@ def _load() -> C.CDLL:
         "pdsp_dev_dwt_tile": ([ll, i32, ll, i32, i32, C.POINTER(ll)], i32),
         "pdsp_dev_upfirdn_tile": ([ll, ll, ll, ll, i32, C.POINTER(ll)], i32),
         "pdsp_dev_complex_op_vec4": ([i32, ll, vp, vp, vp, vp, ll, vp, vp, C.POINTER(i32)], i32),
+        "pdsp_dev_transform_path_f32": ([vp, ll, vp, vp, vp, vp, i32, C.POINTER(i32)], i32),
+        "pdsp_dev_transform_path_f64": ([vp, ll, vp, vp, vp, vp, i32, C.POINTER(i32)], i32),
+        "pdsp_dev_spectrum_path_f32": ([vp, ll, vp, ll, ll, vp, i32, vp, vp, vp, vp, C.c_double, C.POINTER(i32)], i32),
+        "pdsp_dev_spectrum_path_f64": ([vp, ll, vp, ll, ll, vp, i32, vp, vp, vp, vp, C.c_double, C.POINTER(i32)], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

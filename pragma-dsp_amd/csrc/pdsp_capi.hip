@@ -2217,6 +2217,39 @@ int pdsp_dev_complex_op_vec4(int op, long long count, const float *a_re, const f
   return PDSP_OK;
 }
 
+// The planes arrive in the public entry point's order: an inverse is run_complex on the exchanged planes, after
+// pdsp_fft_inverse_*'s own checks
+template <typename T>
+static int transform_path_public(const pdsp_plan *plan, long long batch, const T *re_in, const T *im_in, const T *re_out,
+                                 const T *im_out, int inverse, int *info) {
+  if (!inverse) return transform_path<T>(plan, batch, re_in, im_in, re_out, im_out, info);
+  if (!plan) return fail(PDSP_ERR_BAD_ARG, "plan is null");
+  if (batch > 0 && !re_in) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  return transform_path<T>(plan, batch, im_in, re_in, im_out, re_out, info);
+}
+int pdsp_dev_transform_path_f32(const pdsp_plan *plan, long long batch, const float *re_in, const float *im_in,
+                                const float *re_out, const float *im_out, int inverse, int info[PDSP_DEV_PATH_INFO]) {
+  return transform_path_public<float>(plan, batch, re_in, im_in, re_out, im_out, inverse, info);
+}
+int pdsp_dev_transform_path_f64(const pdsp_plan *plan, long long batch, const double *re_in, const double *im_in,
+                                const double *re_out, const double *im_out, int inverse, int info[PDSP_DEV_PATH_INFO]) {
+  return transform_path_public<double>(plan, batch, re_in, im_in, re_out, im_out, inverse, info);
+}
+int pdsp_dev_spectrum_path_f32(const pdsp_plan *plan, long long batch, const float *frames, long long frame_len,
+                               long long frame_stride, const float *window, int sides, const float *amp_out,
+                               const float *phase_out, const int32_t *peak_idx_out, const pdsp_peak32 *peaks_out,
+                               double sample_rate, int info[PDSP_DEV_PATH_INFO]) {
+  return spectrum_path<float>(plan, batch, frames, frame_len, frame_stride, window, sides, amp_out, phase_out,
+                              peak_idx_out, peaks_out, sample_rate, info);
+}
+int pdsp_dev_spectrum_path_f64(const pdsp_plan *plan, long long batch, const double *frames, long long frame_len,
+                               long long frame_stride, const double *window, int sides, const double *amp_out,
+                               const double *phase_out, const int32_t *peak_idx_out, const pdsp_peak32 *peaks_out,
+                               double sample_rate, int info[PDSP_DEV_PATH_INFO]) {
+  return spectrum_path<double>(plan, batch, frames, frame_len, frame_stride, window, sides, amp_out, phase_out,
+                               peak_idx_out, peaks_out, sample_rate, info);
+}
+
 int pdsp_dev_upfirdn_tile(long long up, long long down, long long ntaps, long long y_len, int elem_bytes,
                           long long info[9]) {
   if (!info) return fail(PDSP_ERR_BAD_ARG, "null buffer");

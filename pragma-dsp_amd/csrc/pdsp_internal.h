@@ -255,6 +255,15 @@ template <typename T>
 int spectrum_impl(const pdsp_plan *plan, long long batch, const T *frames, long long frame_len, long long frame_stride,
                   const T *window, int sides, T *amp_out, T *phase_out, int32_t *peak_idx_out, pdsp_peak32 *peaks_out,
                   double sample_rate, hipStream_t stream);
+// pdsp_dev_transform_path_* / pdsp_dev_spectrum_path_*: the argument checks and the decision of run_complex /
+// spectrum_impl (pdsp_dispatch.inc: Pick) written to info[PDSP_DEV_PATH_INFO]; no HIP call
+template <typename T>
+int transform_path(const pdsp_plan *plan, long long batch, const T *re_in, const T *im_in, const T *re_out,
+                   const T *im_out, int *info);
+template <typename T>
+int spectrum_path(const pdsp_plan *plan, long long batch, const T *frames, long long frame_len, long long frame_stride,
+                  const T *window, int sides, const T *amp_out, const T *phase_out, const int32_t *peak_idx_out,
+                  const pdsp_peak32 *peaks_out, double sample_rate, int *info);
 template <typename T>
 int apply_window_dev(long long batch, long long n, const T *in, const T *window, T *out, hipStream_t s);
 template <typename T, bool PHASE>

@@ -5,6 +5,8 @@
 namespace pdsp_host {
 template int run_complex<float>(const pdsp_plan *, long long, const float *, const float *, float *, float *, float,
                                 hipStream_t);
+template int transform_path<float>(const pdsp_plan *, long long, const float *, const float *, const float *, const float *,
+                                   int *);
 template int run_interleaved<float>(const pdsp_plan *, long long, const float *, float *, bool, hipStream_t);
 template int apply_window_dev<float>(long long, long long, const float *, const float *, float *, hipStream_t);
 template int polar_dev<float, false>(long long, const float *, const float *, float *, hipStream_t);

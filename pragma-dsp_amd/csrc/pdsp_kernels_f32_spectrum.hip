@@ -5,4 +5,6 @@
 namespace pdsp_host {
 template int spectrum_impl<float>(const pdsp_plan *, long long, const float *, long long, long long, const float *, int,
                                   float *, float *, int32_t *, pdsp_peak32 *, double, hipStream_t);
+template int spectrum_path<float>(const pdsp_plan *, long long, const float *, long long, long long, const float *, int,
+                                  const float *, const float *, const int32_t *, const pdsp_peak32 *, double, int *);
 }  // namespace pdsp_host

@@ -1,9 +1,13 @@
 """The f32 transform and spectrum kernels path by path, against f64 references of the f32-rounded inputs.
 
-The dispatcher (pdsp_dispatch.inc: run_complex, launch_rows, spectrum_impl, tile_pass, tilepass_chain) picks among
-about twenty f32 kernel forms by size, plane alignment, aliasing, frame length, stride, window identity, sides,
-requested outputs and four development switches.  expected_path() below mirrors those predicates; every case asserts
-the path it names, and test_path_table_reaches_every_path checks that the tables reach each name in REQUIRED.
+The dispatcher (pdsp_dispatch.inc: pick_transform, pick_spectrum and the launchers that switch on their result) picks
+among about twenty f32 kernel forms by size, plane alignment, aliasing, frame length, stride, window identity, sides,
+requested outputs and four development switches.  expected_path() below restates those predicates independently.
+Before every call the library itself is asked (pdsp_dev_transform_path_f32 / pdsp_dev_spectrum_path_f32, on the
+call's own pointers and under its switch values) which path it takes; path_names() puts the answer into
+expected_path()'s vocabulary and the two sets must be EQUAL, so a change of the dispatch rule fails here and does not
+silently move a case to another kernel.  Every case then asserts the path it names on the library's answer, and
+test_path_table_reaches_every_path checks that the tables reach each name in REQUIRED.
 
 References: numpy.fft in f64 on the f32-rounded inputs (its own error, ~1e-16, is negligible).  Spectrum cases apply
 the scaling of spectrum(): s_edge = 1/N at bins 0 and N/2 one-sided, s_mid = 2/N elsewhere (1/N everywhere two-sided);
@@ -214,6 +218,60 @@ REQUIRED = {
     "fourstep_ab/c-mode1", "bigfft_out<AMP>",
     "peak_wave_kernel", "find_peak_kernel", "peak_from_rows_kernel", "memset",
 }
+
+
+# ---- the dispatch, asked ----------------------------------------------------------------------------------------
+
+PATH_INFO = 17  # PDSP_DEV_PATH_INFO (include/pdsp_hip_dev.h documents the fields)
+ROWS_NAME = {2: "fft_staged_kernel", 3: "fft_stockham_kernel", 4: "fft_split2_kernel", 5: "fft_split4_kernel"}
+TILE_NAME = {1: "tile_pass_kernel", 2: "tile_cols512_kernel", 3: "tile_rows512_kernel"}
+PEAK_NAME = {1: "peak_wave_kernel", 2: "find_peak_kernel", 4: "peak_from_rows_kernel"}
+
+
+def path_names(info, n, spectrum=False):
+    """expected_path()'s names for the decision the library reports in `info`."""
+    (path, rows, n1_rows, n1_square, np_, t0, t1, t2, tile_major, pairs, out_first, fast, wmode, first, fused_peaks,
+     peaks, head) = info
+    L = n.bit_length() - 1
+    tiles = {TILE_NAME[t] for t in (t0, t1, t2)[:np_]}
+    peak = {name for bit, name in PEAK_NAME.items() if peaks & bit}
+    # the N1-point rows of the general four-step path are named where they run like N2-point rows on fft_split4_kernel
+    n1 = {"bigfft-n1-rows", "fft_split4_kernel"} if n1_square and n1_rows == 5 else set()
+    if not spectrum:
+        assert peak == set() and (rows == path or path not in (3, 4, 5)), list(info)
+        if path in (3, 4, 5):
+            return {ROWS_NAME[path]}
+        if path == 8 and np_ == 2:
+            return {"tilepass-2"} | tiles
+        if path == 8:
+            return {"tilepass-3", "tilepass-3-perm" if tile_major else "tilepass-3-natural"} | tiles | \
+                ({"tilepass-3-scratch2"} if pairs == 2 else set())
+        if path == 10:
+            return {"bigfft"} | n1
+        return {{1: "fft_tiny_staged_kernel", 2: "fft_staged_kernel", 7: "fft_paired_kernel", 9: "fourstep-fused"}[path]}
+    peak_tag = "-peak" if fused_peaks else ""
+    if path == 12:
+        names = [{"tilepass_chain-packed"} | tiles, {"fft_split4_kernel-packed"}, {"fft_paired_kernel-packed"}][head]
+        return names | {f"packed-first{first}", "split_amp_rows_kernel"} | peak
+    if path == 14:
+        return {f"spectrum_dif16k_kernel-w{wmode}{peak_tag}"} | peak
+    if path == 15:
+        names = {f"spectrum_packed_kernel-{'FAST' if fast else 'general'}-m{L - 1}-w{wmode}{peak_tag}"}
+        if L == 14 and not fast:
+            names.add("spectrum_packed-16384-general")
+        return names | peak
+    if path == 10:
+        return {"bigfft_out<AMP>"} | n1 | peak
+    return {{9: "fourstep_ab/c-mode1", 11: "memset", 13: "spectrum_staged_kernel", 16: "fft_tiny_staged_kernel<AMP>",
+             17: "small-complex-(x,0)"}[path]} | peak
+
+
+def asked_path(fn, n, *args, spectrum=False):
+    """The names for what the query `fn` reports for a call with these arguments."""
+    import ctypes
+    info = (ctypes.c_int * PATH_INFO)(*([-1] * PATH_INFO))
+    assert fn(*args, info) == 0, _lib().pdsp_last_error()
+    return path_names(list(info), n, spectrum)
 
 
 # ---- buffers ----------------------------------------------------------------------------------------------------
@@ -450,7 +508,11 @@ def run_transform(kind, n, re, im, offs, out_mode="disjoint", switches=None):
         poffs = (offs[0], im_off, offs[2], offs[3])
         checks = [ore, oim]
     s = _stream()
+    mirror = expected_path(kind, n, batch, poffs, aliasing=aliased, switches=switches)
     with Switches(switches):
+        path = asked_path(lib.pdsp_dev_transform_path_f32, n, p._h, batch, bre.ptr, im_ptr, ore_ptr, oim.ptr,
+                          1 if kind == "inverse" else 0)
+        assert path == mirror, (kind, n, batch, poffs, out_mode, switches, sorted(path), sorted(mirror))
         if kind == "complex":
             rc = lib.pdsp_fft_forward_complex_f32(p._h, batch, bre.ptr, im_ptr, ore_ptr, oim.ptr, s)
         elif kind == "real":
@@ -462,7 +524,7 @@ def run_transform(kind, n, re, im, offs, out_mode="disjoint", switches=None):
     for b in checks:
         assert b.outside_ok(), "write outside the output planes"
     got = read_re().astype(np.float64) + 1j * oim.get().astype(np.float64)
-    return got, expected_path(kind, n, batch, poffs, aliasing=aliased, switches=switches)
+    return got, path
 
 
 def reference_transform(kind, re, im):
@@ -620,7 +682,13 @@ def run_spectrum(n, rows, frame_len, stride, f_off, window, w_off, sides, output
     rec = Buf(batch, 4, 0, fill=SENT_I32, dtype=torch.int32) if "rec" in outputs else None
     ptr = lambda b: b.ptr if b is not None else None  # noqa: E731
     two = 1 if sides == "two" else 0
+    mirror = expected_path("spectrum", n, batch, (f_off, w_off if window else None), frame_len=frame_len, stride=stride,
+                           window=window, sides=sides, outputs=outputs, switches=switches)
     with Switches(switches):
+        path = asked_path(lib.pdsp_dev_spectrum_path_f32, n, p._h, batch, fb.ptr, frame_len, stride, wptr, two, ptr(amp),
+                          ptr(ph), ptr(idx), ptr(rec), SR if rec is not None else 1.0, spectrum=True)
+        assert path == mirror, (n, batch, frame_len, stride, f_off, window, w_off, sides, sorted(outputs), switches,
+                                sorted(path), sorted(mirror))
         if rec is not None:
             rc = lib.pdsp_spectrum_peaks_f32(p._h, batch, fb.ptr, frame_len, stride, wptr, two, SR, ptr(amp), ptr(ph),
                                              rec.ptr, _stream())
@@ -633,8 +701,6 @@ def run_spectrum(n, rows, frame_len, stride, f_off, window, w_off, sides, output
         if b is not None:
             assert b.outside_ok(), f"{k}: write outside the output rows"
             out[k] = b.get()
-    path = expected_path("spectrum", n, batch, (f_off, w_off if window else None), frame_len=frame_len, stride=stride,
-                         window=window, sides=sides, outputs=outputs, switches=switches)
     out["path"] = path
     return out
 

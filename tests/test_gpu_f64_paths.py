@@ -1,10 +1,13 @@
 """The f64 transform and spectrum kernels path by path, against long-double references of the exact f64 inputs.
 
-The dispatcher (pdsp_dispatch.inc: run_complex, launch_rows, bigfft_rows, run_interleaved, spectrum_impl) picks among
-the f64 kernel forms by size, batch, plane alignment (offsets of 1, 2 and 4 doubles give 8-, 16- and 32-byte
-alignment), aliasing, frame length, stride, window, sides, requested outputs and three development switches.
-expected_path_f64() below mirrors those predicates for T = double; every case asserts the path it names, and
-tests/test_f64_paths_cpu.py checks (without a GPU) that the tables reach each name in REQUIRED_F64.  f64 has no peak
+The dispatcher (pdsp_dispatch.inc: pick_transform, pick_spectrum and the launchers that switch on their result;
+run_interleaved) picks among the f64 kernel forms by size, batch, plane alignment (offsets of 1, 2 and 4 doubles give
+8-, 16- and 32-byte alignment), aliasing, frame length, stride, window, sides, requested outputs and three development
+switches.  expected_path_f64() below restates those predicates for T = double, independently.  Before every call the
+library itself is asked (pdsp_dev_transform_path_f64 / pdsp_dev_spectrum_path_f64, on the call's own pointers and
+under its switch values); path_names_f64() puts the answer into the same vocabulary and the two sets must be EQUAL.
+Every case then asserts the path it names on the library's answer, and tests/test_f64_paths_cpu.py checks (without a
+GPU) that the tables reach each name in REQUIRED_F64.  f64 has no peak
 records (pdsp_spectrum_peaks_f32 only), so of the three peak kernels it reaches peak_wave_kernel and find_peak_kernel.
 
 References: numpy.fft on np.longdouble input, which numpy 2.x computes in x86 80-bit precision (complex256, eps
@@ -34,7 +37,7 @@ test_gpu_f64_dispatch.py's 1e-14 / 1e-13 of max|X| is 50-100x above these bounds
 import numpy as np
 import pytest
 
-from test_gpu_f32_paths import Buf, Switches, Worst, lg, scale, SENT_I32
+from test_gpu_f32_paths import Buf, Switches, Worst, lg, scale, SENT_I32, PATH_INFO, ROWS_NAME, PEAK_NAME
 
 pytestmark = pytest.mark.gpu
 
@@ -145,6 +148,42 @@ REQUIRED_F64 = {
     *[f"spectrum_packed_kernel-{f}-m{m}-w{w}" for f in ("FAST", "general") for m in range(5, 14) for w in (0, 1)],
     "fourstep_out_kernel<AMP>", "bigfft_out<AMP>", "peak_wave_kernel", "find_peak_kernel", "memset",
 }
+
+
+# ---- the dispatch, asked ----------------------------------------------------------------------------------------
+
+def path_names_f64(info, n, spectrum=False):
+    """expected_path_f64()'s names for the decision the library reports in `info` (include/pdsp_hip_dev.h)."""
+    (path, rows, n1_rows, n1_square, np_, t0, t1, t2, tile_major, pairs, out_first, fast, wmode, first, fused_peaks,
+     peaks, head) = info
+    L = n.bit_length() - 1
+    assert np_ == 0 and not fused_peaks and path not in (5, 7, 8, 12, 13, 14), list(info)  # the f32-only forms
+    peak = {name for bit, name in PEAK_NAME.items() if peaks & bit}
+    bigrows = set()
+    if path == 10:
+        form = "bigfft-n1-split2" if n1_square else {2: "bigfft-n1-staged", 3: "bigfft-n1-stockham-tw1"}[n1_rows]
+        bigrows = {form, ROWS_NAME[n1_rows], ROWS_NAME[rows]}
+    if not spectrum:
+        assert peak == set(), list(info)
+        if path == 10:
+            assert pairs == (1 if out_first else 2), list(info)
+            return {"bigfft", "bigfft-out-scratch" if out_first else "bigfft-scratch4"} | bigrows
+        return {{1: "fft_tiny_staged_kernel", 2: "fft_staged_kernel", 3: "fft_stockham_kernel", 4: "fft_split2_kernel",
+                 6: "fft_real_kernel", 9: "fourstep-fused"}[path]}
+    if path == 15:
+        return {f"spectrum_packed_kernel-{'FAST' if fast else 'general'}-m{L - 1}-w{wmode}"} | peak
+    if path == 10:
+        return {"bigfft_out<AMP>"} | bigrows | peak
+    return {{9: "fourstep_out_kernel<AMP>", 11: "memset", 16: "fft_tiny_staged_kernel<AMP>",
+             17: "small-complex-(x,0)"}[path]} | peak
+
+
+def asked_path(fn, n, *args, spectrum=False):
+    """The names for what the query `fn` reports for a call with these arguments."""
+    import ctypes
+    info = (ctypes.c_int * PATH_INFO)(*([-1] * PATH_INFO))
+    assert fn(*args, info) == 0, _lib().pdsp_last_error()
+    return path_names_f64(list(info), n, spectrum)
 
 
 # ---- extended-precision references ------------------------------------------------------------------------------
@@ -324,7 +363,11 @@ def run_transform(kind, n, re, im, offs, out_mode="disjoint", switches=None):
         poffs = (offs[0], im_off, offs[2], offs[3])
         checks = [ore, oim]
     s = _stream()
+    mirror = expected_path_f64(kind, n, batch, poffs, aliasing=out_mode != "disjoint", switches=switches)
     with Switches(switches):
+        path = asked_path(lib.pdsp_dev_transform_path_f64, n, p._h, batch, bre.ptr, im_ptr, ore_ptr, oim.ptr,
+                          1 if kind == "inverse" else 0)
+        assert path == mirror, (kind, n, batch, poffs, out_mode, switches, sorted(path), sorted(mirror))
         if kind == "complex":
             rc = lib.pdsp_fft_forward_complex_f64(p._h, batch, bre.ptr, im_ptr, ore_ptr, oim.ptr, s)
         elif kind == "real":
@@ -336,7 +379,7 @@ def run_transform(kind, n, re, im, offs, out_mode="disjoint", switches=None):
     for b in checks:
         assert b.outside_ok(), "write outside the output planes"
     got = read_re() + 1j * oim.get()
-    return got, expected_path_f64(kind, n, batch, poffs, aliasing=out_mode != "disjoint", switches=switches)
+    return got, path
 
 
 def _tf_kind(kind):
@@ -538,7 +581,13 @@ def run_spectrum(n, rows, frame_len, stride, f_off, window, w_off, sides, output
     ph = dbuf(batch, bins, 1) if "ph" in outputs else None
     idx = Buf(batch, 1, 0, fill=SENT_I32, dtype=torch.int32) if "idx" in outputs else None
     ptr = lambda b: b.ptr if b is not None else None  # noqa: E731
+    mirror = expected_path_f64("spectrum", n, batch, (f_off, w_off if window else None), frame_len=frame_len,
+                               stride=stride, window=window, sides=sides, outputs=outputs, switches=switches)
     with Switches(switches):
+        path = asked_path(lib.pdsp_dev_spectrum_path_f64, n, p._h, batch, fb.ptr, frame_len, stride, wptr,
+                          1 if sides == "two" else 0, ptr(amp), ptr(ph), ptr(idx), None, 1.0, spectrum=True)
+        assert path == mirror, (n, batch, frame_len, stride, f_off, window, w_off, sides, sorted(outputs), switches,
+                                sorted(path), sorted(mirror))
         rc = lib.pdsp_spectrum_f64(p._h, batch, fb.ptr, frame_len, stride, wptr, 1 if sides == "two" else 0, ptr(amp),
                                    ptr(ph), ptr(idx), _stream())
         torch.cuda.synchronize()
@@ -548,8 +597,7 @@ def run_spectrum(n, rows, frame_len, stride, f_off, window, w_off, sides, output
         if b is not None:
             assert b.outside_ok(), f"{k}: write outside the output rows"
             out[k] = b.get()
-    out["path"] = expected_path_f64("spectrum", n, batch, (f_off, w_off if window else None), frame_len=frame_len,
-                                    stride=stride, window=window, sides=sides, outputs=outputs, switches=switches)
+    out["path"] = path
     return out
 
 
