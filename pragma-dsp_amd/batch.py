@@ -10,21 +10,14 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _device
 from ._capi import PdspError, check, lib
+from ._device import COMPLEX, operand
+from ._device import ptr as _ptr, stream_ptr as _stream_ptr  # noqa: F401  (stream.py and tests take them from here)
 from .core import isPowerOfTwo, js_num
 from .fourier import createWindow
-
-
-def _stream_ptr(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 class PlanWindow:
@@ -47,45 +40,28 @@ class PlanWindow:
         return torch.from_numpy(createWindow(self.kind, self.shape[0])).to(self.dtype).to(self.device)
 
 
-class BatchedFft:
+class BatchedFft(_device.Handle):
     """One plan, many rows.  Tensors are contiguous, shape [..., N], on the plan's GPU, of the
     plan's dtype: torch.float32 (default; sizes up to 2^28) or torch.float64 (up to 2^26; single-pass
     transforms up to N = 8192, spectrum up to N = 16384, four-step beyond)."""
 
+    _destroy = lib.pdsp_plan_destroy
+
     def __init__(self, size, device=None, dtype=torch.float32):
-        if dtype not in (torch.float32, torch.float64):
-            raise PdspError(_capi.ERR_BAD_ARG, f"unsupported dtype {dtype}")
-        self.dtype = dtype
-        self._sfx = "f32" if dtype == torch.float32 else "f64"
+        _device.suffix(dtype)
         if not isPowerOfTwo(size):
             raise PdspError(_capi.ERR_SIZE_NOT_POW2, f"FFT size must be power of two, got {js_num(size)}")
-        if not torch.cuda.is_available():
-            raise PdspError(_capi.ERR_DEVICE, "no HIP device available (the pdsp engine has no CPU fallback)")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
         self.size = int(size)
-        handle = C.c_void_p()
-        check(lib.pdsp_plan_create(self.size, self.device.index, C.byref(handle)))
-        self._h = handle
         self._windows = {}
         self.arena = None  # the allocation behind the planes of the last alloc_planes() call, if any
+        self._open(lambda dev, out: lib.pdsp_plan_create(self.size, dev, out), device, dtype)
 
     def close(self):
         """Destroys the native plan now (also done when the object is collected).  For a size beyond the single-pass
         limit this also hands the engine's scratch planes -- as large as the largest such transform run -- back to
         the device, where the caller's allocator can use them again."""
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib.pdsp_plan_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-            self._windows = {}
-
-    def __del__(self):
-        self.close()
+        super().close()
+        self._windows = {}
 
     def __enter__(self):
         return self
@@ -95,22 +71,22 @@ class BatchedFft:
         return False
 
     # -- helpers -------------------------------------------------------------
-    def _check(self, t, name, last=None):
-        if t.dtype != self.dtype or not t.is_cuda or not t.is_contiguous():
-            raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be a contiguous {self.dtype} tensor on {self.device}")
-        if t.device != self.device:
-            raise PdspError(_capi.ERR_BAD_ARG, f"{name} is on {t.device}, plan is on {self.device}")
-        want = self.size if last is None else last
-        if t.shape[-1] != want:
-            raise PdspError(_capi.ERR_INPUT_LENGTH, f"FFT input length {t.shape[-1]} != size {want}")
+    def _plane(self, t, name, count):
+        operand(t, name, self.device, self.dtype, last=self.size)
+        if t.numel() != count:
+            raise PdspError(_capi.ERR_BAD_ARG, f"{name} has {t.numel()} elements, input.real has {count}")
+        return t
 
-    def _out(self, like, out):
-        if out is not None:
-            ore, oim = out
-            self._check(ore, "out.real")
-            self._check(oim, "out.imag")
-            return ore, oim
-        return torch.empty_like(like), torch.empty_like(like)
+    def _planes(self, re, im, out):
+        """The operands of forward / inverse: (batch, out.real, out.imag).  Every plane is [..., N] with the element
+        count of re -- the count, not the shape: callers pass reshaped views."""
+        operand(re, "input.real", self.device, self.dtype, last=self.size)
+        count = re.numel()
+        if im is not None:
+            self._plane(im, "input.imag", count)
+        if out is None:
+            return count // self.size, torch.empty_like(re), torch.empty_like(re)
+        return count // self.size, self._plane(out[0], "out.real", count), self._plane(out[1], "out.imag", count)
 
     def window(self, kind: str) -> PlanWindow:
         """The plan's device copy of createWindow(kind, N), cached per kind like FourierLive's window
@@ -167,23 +143,19 @@ class BatchedFft:
     # -- transforms ------------------------------------------------------------
     def forward(self, re: torch.Tensor, im: torch.Tensor | None = None, out=None):
         """Rows of Radix2Fft.forward (im None) or .forwardComplex."""
-        self._check(re, "input.real")
-        batch = re.numel() // self.size if self.size else 0
-        ore, oim = self._out(re, out)
+        batch, ore, oim = self._planes(re, im, out)
         s = _stream_ptr(self.device)
         if im is None:
             check(getattr(lib, "pdsp_fft_forward_real_" + self._sfx)(self._h, batch, _ptr(re), _ptr(ore), _ptr(oim), s))
         else:
-            self._check(im, "input.imag")
             check(getattr(lib, "pdsp_fft_forward_complex_" + self._sfx)(self._h, batch, _ptr(re), _ptr(im), _ptr(ore),
                                                                       _ptr(oim), s))
         return ore, oim
 
     def inverse(self, re: torch.Tensor, im: torch.Tensor, out=None):
-        self._check(re, "input.real")
-        self._check(im, "input.imag")
-        batch = re.numel() // self.size
-        ore, oim = self._out(re, out)
+        if im is None:
+            raise PdspError(_capi.ERR_BAD_ARG, "the inverse needs both planes")
+        batch, ore, oim = self._planes(re, im, out)
         check(getattr(lib, "pdsp_fft_inverse_" + self._sfx)(self._h, batch, _ptr(re), _ptr(im), _ptr(ore), _ptr(oim),
                                                           _stream_ptr(self.device)))
         return ore, oim
@@ -191,15 +163,11 @@ class BatchedFft:
     def forward_interleaved(self, z: torch.Tensor, out: torch.Tensor | None = None, inverse: bool = False):
         """forwardComplex (or inverse) on rows of a complex64 / complex128 tensor [..., N] -- the
         interleaved (re, im) layout of I/Q streams.  Single-pass sizes only."""
-        want = torch.complex64 if self.dtype == torch.float32 else torch.complex128
-        if z.dtype != want or not z.is_cuda or not z.is_contiguous() or z.device != self.device:
-            raise PdspError(_capi.ERR_BAD_ARG, f"input must be a contiguous {want} tensor on {self.device}")
-        if z.shape[-1] != self.size:
-            raise PdspError(_capi.ERR_INPUT_LENGTH, f"FFT input length {z.shape[-1]} != size {self.size}")
+        operand(z, "input", self.device, COMPLEX[self.dtype], last=self.size)
         if out is None:
             out = torch.empty_like(z)
-        elif out.dtype != want or out.shape != z.shape or not out.is_contiguous() or out.device != self.device:
-            raise PdspError(_capi.ERR_BAD_ARG, "out must match the input's dtype, shape and device")
+        else:
+            operand(out, "out", self.device, z.dtype, shape=z.shape)
         fn = getattr(lib, ("pdsp_fft_inverse_interleaved_" if inverse else "pdsp_fft_forward_interleaved_") + self._sfx)
         check(fn(self._h, z.numel() // self.size, _ptr(z), _ptr(out), _stream_ptr(self.device)))
         return out
@@ -207,74 +175,13 @@ class BatchedFft:
     def inverse_interleaved(self, z: torch.Tensor, out: torch.Tensor | None = None):
         return self.forward_interleaved(z, out, inverse=True)
 
-    def spectrum(self, frames: torch.Tensor, window="rect", sides: str = "one", want_phase: bool = False,
-                 want_peak: bool = False, out=None):
-        """Rows of spectrum()'s body: frames [..., L] (L <= N zero-padded, L > N
-        truncated: spectrum.ts:36-43) -> amplitude [..., bins] (+ phase, + peak bin)."""
-        if frames.dtype != self.dtype or not frames.is_cuda or not frames.is_contiguous():
-            raise PdspError(_capi.ERR_BAD_ARG, f"frames must be a contiguous {self.dtype} CUDA tensor")
-        if frames.get_device() != self.device.index:
-            raise PdspError(_capi.ERR_BAD_ARG, f"frames are on {frames.device}, plan is on {self.device}")
-        length = frames.shape[-1]
-        batch = frames.numel() // length if length else 0
-        two = sides != "one"
-        bins = self.size if two else self.size // 2 + 1
-        shape = tuple(frames.shape[:-1])
-        # the amplitude rows are written through a raw pointer: exactly [..., bins], contiguous, on the plan's device
-        if out is not None and (out.get_device() != self.device.index or out.dtype != self.dtype
-                                or not out.is_contiguous() or out.shape != shape + (bins,)):
-            raise PdspError(_capi.ERR_BAD_ARG, f"out must be a contiguous {self.dtype} tensor of shape "
-                                               f"{shape + (bins,)} on {self.device}")
-        if isinstance(window, str):
-            if self.size != 1 and window not in _capi.WINDOW_TYPES:
-                raise PdspError(_capi.ERR_WINDOW_TYPE, f"Unsupported window type: {window}")
-            win = None if (window == "rect" or self.size == 1) else self.window(window)
-        else:
-            win = window
-            if win is not None:
-                if win.shape[-1] != self.size:
-                    raise PdspError(_capi.ERR_WINDOW_LENGTH, "Window length must match input length.")
-                if not isinstance(win, PlanWindow):
-                    self._check(win, "window")
-        amp = out if out is not None else torch.empty(shape + (bins,), dtype=self.dtype, device=self.device)
-        ph = torch.empty(shape + (bins,), dtype=self.dtype, device=self.device) if want_phase else None
-        pk = torch.empty(shape, dtype=torch.int32, device=self.device) if want_peak else None
-        check(getattr(lib, "pdsp_spectrum_" + self._sfx)(self._h, batch, _ptr(frames), min(length, self.size), length, _ptr(win),
-                                    1 if two else 0, _ptr(amp), _ptr(ph), _ptr(pk), _stream_ptr(self.device)))
-        return amp, ph, pk
-
-
-    def stft(self, signal: torch.Tensor, hop: int, window="hann", sides: str = "one", want_phase: bool = False,
-             want_peak: bool = False):
-        """Short-time transform of one contiguous 1-D signal: frame b = signal[b*hop : b*hop + N], the
-        body of spectrum() on every frame.  The frames are never materialised -- the kernels read the
-        signal with row stride `hop`, so overlapping frames cost no extra HBM footprint.  Returns
-        (amplitude [frames, bins], phase or None, peak bin or None)."""
-        if signal.dim() != 1 or signal.dtype != self.dtype or not signal.is_cuda or not signal.is_contiguous():
-            raise PdspError(_capi.ERR_BAD_ARG, f"signal must be a contiguous 1-D {self.dtype} CUDA tensor")
-        if signal.get_device() != self.device.index:
-            raise PdspError(_capi.ERR_BAD_ARG, f"signal is on {signal.device}, plan is on {self.device}")
-        if hop < 1:
-            raise PdspError(_capi.ERR_BAD_ARG, f"hop must be >= 1, got {hop}")
-        n = self.size
-        if signal.numel() < n:
-            raise PdspError(_capi.ERR_INPUT_LENGTH, f"signal length {signal.numel()} is shorter than one frame ({n})")
-        frames = 1 + (signal.numel() - n) // hop
-        two = sides != "one"
-        bins = n if two else n // 2 + 1
-        if self.size != 1 and window not in _capi.WINDOW_TYPES:
-            raise PdspError(_capi.ERR_WINDOW_TYPE, f"Unsupported window type: {window}")
-        win = None if (window == "rect" or n == 1) else self.window(window)
-        amp = torch.empty((frames, bins), dtype=self.dtype, device=self.device)
-        ph = torch.empty((frames, bins), dtype=self.dtype, device=self.device) if want_phase else None
-        pk = torch.empty((frames,), dtype=torch.int32, device=self.device) if want_peak else None
-        check(getattr(lib, "pdsp_spectrum_" + self._sfx)(self._h, frames, _ptr(signal), n, int(hop), _ptr(win), 1 if two else 0,
-                                                         _ptr(amp), _ptr(ph), _ptr(pk), _stream_ptr(self.device)))
-        return amp, ph, pk
-
-    def _table_window(self, window, name="window"):
-        """A window argument of the short-time pair: a type name (the plan's table; "rect" = none), a PlanWindow of
-        this plan, or a contiguous device tensor of N values in the plan's dtype."""
+    # -- what the spectrum and short-time methods share ---------------------------
+    def _table_window(self, window, name="window", spectral=False):
+        """A window argument: a type name (the plan's table; "rect" = none), a PlanWindow of this plan, or a contiguous
+        device tensor of N values in the plan's dtype.  The spectrum family (`spectral`) also takes None, and at
+        N = 1, where the reference never builds a window, any name."""
+        if spectral and (window is None or (self.size == 1 and isinstance(window, str))):
+            return None
         if isinstance(window, str):
             if window not in _capi.WINDOW_TYPES:
                 raise PdspError(_capi.ERR_WINDOW_TYPE, f"Unsupported window type: {window}")
@@ -287,28 +194,74 @@ class BatchedFft:
             raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be a window type name or a device tensor")
         if window.dim() != 1 or window.shape[0] != self.size:
             raise PdspError(_capi.ERR_WINDOW_LENGTH, "Window length must match input length.")
-        self._check(window, name)
+        operand(window, name, self.device, self.dtype)
         return window
+
+    def _frames(self, frames):
+        """frames [..., L], contiguous -> (batch, L, the shape of one output value per frame)."""
+        operand(frames, "frames", self.device, self.dtype)
+        length = frames.shape[-1]
+        return (frames.numel() // length if length else 0), length, tuple(frames.shape[:-1])
+
+    def _signal(self, signal, hop):
+        """One contiguous 1-D signal of at least one frame -> (hop, frames)."""
+        operand(signal, "signal", self.device, self.dtype, ndim=1)
+        if int(hop) < 1:
+            raise PdspError(_capi.ERR_BAD_ARG, f"hop must be >= 1, got {hop}")
+        if signal.numel() < self.size:
+            raise PdspError(_capi.ERR_INPUT_LENGTH,
+                            f"signal length {signal.numel()} is shorter than one frame ({self.size})")
+        return int(hop), 1 + (signal.numel() - self.size) // int(hop)
+
+    def _bins(self, sides):
+        return self.size // 2 + 1 if sides == "one" else self.size
+
+    def _outputs(self, shape, bins, amp, phase, peak):
+        """Fresh outputs of the spectrum family: amplitude and phase [..., bins] in the plan's dtype and the int32 peak
+        output [..., *peak], each only where asked for (else None)."""
+        def new(tail, dtype=self.dtype):
+            return torch.empty(shape + tail, dtype=dtype, device=self.device)
+        return (new((bins,)) if amp else None, new((bins,)) if phase else None,
+                new(peak, torch.int32) if peak is not None else None)
+
+    def spectrum(self, frames: torch.Tensor, window="rect", sides: str = "one", want_phase: bool = False,
+                 want_peak: bool = False, out=None):
+        """Rows of spectrum()'s body: frames [..., L] (L <= N zero-padded, L > N
+        truncated: spectrum.ts:36-43) -> amplitude [..., bins] (+ phase, + peak bin)."""
+        batch, length, shape = self._frames(frames)
+        bins = self._bins(sides)
+        # the amplitude rows are written through a raw pointer: exactly [..., bins], contiguous, on the plan's device
+        if out is not None:
+            operand(out, "out", self.device, self.dtype, shape=shape + (bins,))
+        win = self._table_window(window, spectral=True)
+        amp, ph, pk = self._outputs(shape, bins, out is None, want_phase, () if want_peak else None)
+        amp = out if out is not None else amp
+        check(getattr(lib, "pdsp_spectrum_" + self._sfx)(self._h, batch, _ptr(frames), min(length, self.size), length, _ptr(win),
+                                    int(sides != "one"), _ptr(amp), _ptr(ph), _ptr(pk), _stream_ptr(self.device)))
+        return amp, ph, pk
+
+    def stft(self, signal: torch.Tensor, hop: int, window="hann", sides: str = "one", want_phase: bool = False,
+             want_peak: bool = False):
+        """Short-time transform of one contiguous 1-D signal: frame b = signal[b*hop : b*hop + N], the
+        body of spectrum() on every frame.  The frames are never materialised -- the kernels read the
+        signal with row stride `hop`, so overlapping frames cost no extra HBM footprint.  Returns
+        (amplitude [frames, bins], phase or None, peak bin or None)."""
+        hop, frames = self._signal(signal, hop)
+        win = self._table_window(window, spectral=True)
+        amp, ph, pk = self._outputs((frames,), self._bins(sides), True, want_phase, () if want_peak else None)
+        check(getattr(lib, "pdsp_spectrum_" + self._sfx)(self._h, frames, _ptr(signal), self.size, hop, _ptr(win),
+                                                         int(sides != "one"), _ptr(amp), _ptr(ph), _ptr(pk),
+                                                         _stream_ptr(self.device)))
+        return amp, ph, pk
 
     def stft_complex(self, signal: torch.Tensor, hop: int, window="hann"):
         """Complex short-time transform of one contiguous 1-D signal: frame b = signal[b*hop : b*hop + N], the tail
         shorter than a hop ignored (as stft()).  Returns (re, im), each [frames, N/2 + 1]: the one-sided DFT of
         w * frame, unscaled.  One launch; the frames are read in place at row stride `hop`.  64 <= N <= 16384."""
-        if not isinstance(signal, torch.Tensor) or signal.dim() != 1 or signal.dtype != self.dtype or not signal.is_cuda \
-                or not signal.is_contiguous():
-            raise PdspError(_capi.ERR_BAD_ARG, f"signal must be a contiguous 1-D {self.dtype} CUDA tensor")
-        if signal.get_device() != self.device.index:
-            raise PdspError(_capi.ERR_BAD_ARG, f"signal is on {signal.device}, plan is on {self.device}")
-        if int(hop) < 1:
-            raise PdspError(_capi.ERR_BAD_ARG, f"hop must be >= 1, got {hop}")
-        n = self.size
-        if signal.numel() < n:
-            raise PdspError(_capi.ERR_INPUT_LENGTH, f"signal length {signal.numel()} is shorter than one frame ({n})")
+        hop, frames = self._signal(signal, hop)
         win = self._table_window(window)
-        frames = 1 + (signal.numel() - n) // int(hop)
-        re = torch.empty((frames, n // 2 + 1), dtype=self.dtype, device=self.device)
-        im = torch.empty_like(re)
-        check(getattr(lib, "pdsp_stft_complex_" + self._sfx)(self._h, frames, _ptr(signal), n, int(hop), _ptr(win),
+        re, im, _ = self._outputs((frames,), self.size // 2 + 1, True, True, None)  # two planes [frames, bins]
+        check(getattr(lib, "pdsp_stft_complex_" + self._sfx)(self._h, frames, _ptr(signal), self.size, hop, _ptr(win),
                                                              _ptr(re), _ptr(im), _stream_ptr(self.device)))
         return re, im
 
@@ -317,11 +270,8 @@ class BatchedFft:
         pdsp_istft_*): [(frames - 1) * hop + N] samples, sum_b w y_b / sum_b w^2 over the frames covering each
         sample, 0 where that denominator is <= 1e-11.  Bit-identical from call to call."""
         n = self.size
-        bins = n // 2 + 1
         for t, name in ((re, "re"), (im, "im")):
-            if not isinstance(t, torch.Tensor) or t.dim() != 2:
-                raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be a 2-D tensor [frames, N/2 + 1]")
-            self._check(t, name, last=bins)
+            operand(t, name, self.device, self.dtype, ndim=2, last=n // 2 + 1)
         if re.shape != im.shape:
             raise PdspError(_capi.ERR_BAD_ARG, f"re {tuple(re.shape)} and im {tuple(im.shape)} differ in shape")
         frames = re.shape[0]
@@ -334,9 +284,7 @@ class BatchedFft:
         if out is None:
             out = torch.empty((total,), dtype=self.dtype, device=self.device)
         else:
-            if not isinstance(out, torch.Tensor) or out.dim() != 1:
-                raise PdspError(_capi.ERR_BAD_ARG, f"out must be a 1-D tensor of {total} samples")
-            self._check(out, "out", last=total)
+            operand(out, "out", self.device, self.dtype, ndim=1, last=total)
         check(getattr(lib, "pdsp_istft_" + self._sfx)(self._h, frames, _ptr(re), _ptr(im), int(hop), _ptr(win), _ptr(out),
                                                       _stream_ptr(self.device)))
         return out
@@ -344,20 +292,10 @@ class BatchedFft:
     def _dct_call(self, x, type, norm, out, name):
         """Validation shared by dct / idct: x [rows, N] with contiguous rows at any row stride >= N (x.stride(0));
         out None, x itself (exact in place) or a tensor of the same shape with its own row stride."""
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise PdspError(_capi.ERR_BAD_ARG, f"{name}: x must be a 2-D tensor [rows, N]")
         n = self.size
-        for t, tn in ((x, "x"), (out, "out")):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor) or t.dim() != 2:
-                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: {tn} must be a 2-D tensor [rows, N]")
-            if t.dtype != self.dtype or not t.is_cuda or t.device != self.device:
-                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: {tn} must be a {self.dtype} tensor on {self.device}")
-            if t.shape[-1] != n:
-                raise PdspError(_capi.ERR_INPUT_LENGTH, f"FFT input length {t.shape[-1]} != size {n}")
-            if t.shape[0] > 1 and t.stride(0) < n or t.stride(1) != 1:
-                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: {tn} needs contiguous rows at a row stride >= N")
+        operand(x, f"{name}: x", self.device, self.dtype, ndim=2, last=n, layout="strided")
+        if out is not None:
+            operand(out, f"{name}: out", self.device, self.dtype, ndim=2, last=n, layout="strided")
         if out is not None and out.shape != x.shape:
             raise PdspError(_capi.ERR_BAD_ARG, f"{name}: out {tuple(out.shape)} and x {tuple(x.shape)} differ in shape")
         if type not in (2, 3):
@@ -402,32 +340,18 @@ class BatchedFft:
         stride; x is out itself, or out[:, :len] when len < N)."""
         n = self.size
         analytic = mode == "analytic"
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise PdspError(_capi.ERR_BAD_ARG, f"{name}: x must be a 2-D tensor [rows, len]")
-        if x.dtype != self.dtype or not x.is_cuda or x.device != self.device:
-            raise PdspError(_capi.ERR_BAD_ARG, f"{name}: x must be a {self.dtype} tensor on {self.device}")
+        operand(x, f"{name}: x", self.device, self.dtype, ndim=2, layout="strided")
         rows, ln = x.shape
         if rows < 1:
             raise PdspError(_capi.ERR_BAD_ARG, "batch must be >= 1, got 0")
         if ln < 1 or ln > n:
             raise PdspError(_capi.ERR_BAD_ARG, f"len must be 1 ... N = {n}, got {ln}")
-        if rows > 1 and x.stride(0) < ln or (ln > 1 and x.stride(1) != 1):
-            raise PdspError(_capi.ERR_BAD_ARG, f"{name}: x needs contiguous rows at a row stride >= len")
-        odt = self.dtype
-        if analytic:
-            odt = torch.complex64 if self.dtype == torch.float32 else torch.complex128
+        odt = COMPLEX[self.dtype] if analytic else self.dtype
         k = 2 if analytic else 1  # plan-dtype values per output element
         if out is None:
             out = torch.empty((rows, n), dtype=odt, device=self.device)
         else:
-            if not isinstance(out, torch.Tensor) or out.dim() != 2:
-                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: out must be a 2-D tensor [rows, N]")
-            if out.dtype != odt or not out.is_cuda or out.device != self.device:
-                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: out must be a {odt} tensor on {self.device}")
-            if tuple(out.shape) != (rows, n):
-                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: out {tuple(out.shape)} must be [{rows}, {n}]")
-            if rows > 1 and out.stride(0) < n or out.stride(1) != 1:
-                raise PdspError(_capi.ERR_BAD_ARG, f"{name}: out needs contiguous rows at a row stride >= N")
+            operand(out, f"{name}: out", self.device, odt, ndim=2, shape=(rows, n), layout="strided")
         xs = x.stride(0) if rows > 1 else max(ln, n)
         ys = k * out.stride(0) if rows > 1 else k * n
         if out.data_ptr() == x.data_ptr() and not analytic:
@@ -468,28 +392,14 @@ class BatchedFft:
         per frame leave the kernel."""
         if self.dtype != torch.float32:
             raise PdspError(_capi.ERR_BAD_ARG, "spectrum_peaks is f32 only (16-byte f32 records)")
-        if frames.dtype != torch.float32 or not frames.is_cuda or not frames.is_contiguous():
-            raise PdspError(_capi.ERR_BAD_ARG, "frames must be a contiguous float32 CUDA tensor")
-        if frames.get_device() != self.device.index:
-            raise PdspError(_capi.ERR_BAD_ARG, f"frames are on {frames.device}, plan is on {self.device}")
+        batch, length, shape = self._frames(frames)
         if sample_rate <= 0:
             raise PdspError(_capi.ERR_SAMPLE_RATE, f"Sample rate must be positive, got {js_num(sample_rate)}")
-        length = frames.shape[-1]
-        batch = frames.numel() // length if length else 0
-        two = sides != "one"
-        bins = self.size if two else self.size // 2 + 1
-        if isinstance(window, str):
-            if self.size != 1 and window not in _capi.WINDOW_TYPES:
-                raise PdspError(_capi.ERR_WINDOW_TYPE, f"Unsupported window type: {window}")
-            win = None if (window == "rect" or self.size == 1) else self.window(window)
-        else:
-            win = window
-        shape = tuple(frames.shape[:-1])
-        amp = torch.empty(shape + (bins,), dtype=torch.float32, device=self.device) if (want_amp or want_phase) else None
-        ph = torch.empty(shape + (bins,), dtype=torch.float32, device=self.device) if want_phase else None
-        rec = torch.empty(shape + (4,), dtype=torch.int32, device=self.device)  # pdsp_peak32 records
+        win = self._table_window(window, spectral=True)
+        # rec: pdsp_peak32 records
+        amp, ph, rec = self._outputs(shape, self._bins(sides), want_amp or want_phase, want_phase, (4,))
         check(lib.pdsp_spectrum_peaks_f32(self._h, batch, _ptr(frames), min(length, self.size), length, _ptr(win),
-                                          1 if two else 0, float(sample_rate), _ptr(amp), _ptr(ph), _ptr(rec),
+                                          int(sides != "one"), float(sample_rate), _ptr(amp), _ptr(ph), _ptr(rec),
                                           _stream_ptr(self.device)))
         f = rec.view(torch.float32)
         return rec[..., 0], f[..., 1], f[..., 2], f[..., 3], amp, ph
@@ -500,32 +410,13 @@ class BatchedFft:
 # checked here, before any library call: a CUDA tensor, contiguous, on the device and of the dtype of the first
 # operand, with the element count the call reads or writes.
 
-_SFX = {torch.float32: "f32", torch.float64: "f64"}
-
-
 def _check_operand(t, name, like=None, numel=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be a CUDA tensor")
-    if like is not None and t.device != like.device:
-        raise PdspError(_capi.ERR_BAD_ARG, f"{name} is on {t.device}, the first operand on {like.device}")
-    if like is not None and t.dtype != like.dtype:
-        raise PdspError(_capi.ERR_BAD_ARG, f"{name} is {t.dtype}, the first operand {like.dtype}")
-    if not t.is_contiguous():
-        raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be contiguous")
-    if numel is not None and t.numel() != numel:
-        raise PdspError(_capi.ERR_INPUT_LENGTH, f"{name} has {t.numel()} elements, {numel} expected")
-
-
-def _sfx(t, what):
-    sfx = _SFX.get(t.dtype)
-    if sfx is None:
-        raise PdspError(_capi.ERR_BAD_ARG, f"{what}: unsupported dtype {t.dtype} (float32 or float64)")
-    return sfx
+    operand(t, name, like.device if like is not None else None, like.dtype if like is not None else None, numel=numel)
 
 
 def apply_window(frames: torch.Tensor, window: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     _check_operand(frames, "frames")
-    sfx = _sfx(frames, "apply_window")
+    sfx = _device.suffix(frames.dtype, "apply_window")
     _check_operand(window, "window", frames)
     n = frames.shape[-1] if frames.dim() else 1
     if window.numel() != n or window.shape[-1:] != (n,):
@@ -540,7 +431,7 @@ def apply_window(frames: torch.Tensor, window: torch.Tensor, out: torch.Tensor |
 
 def _polar(name, re, im, out):
     _check_operand(re, "re")
-    sfx = _sfx(re, name)
+    sfx = _device.suffix(re.dtype, name)
     _check_operand(im, "im", re, re.numel())
     if out is not None:
         _check_operand(out, "out", re, re.numel())

@@ -85,7 +85,9 @@ class Czt(ChirpRows):
     """A pdsp_czt on one GPU: the pre, post and chirp-filter tables of one transform, both precisions."""
 
     _destroy = lib.pdsp_czt_destroy
-    _forward = (lib.pdsp_czt_f32, lib.pdsp_czt_f64)
+
+    def _entry(self, sfx):
+        return getattr(lib, "pdsp_czt_" + sfx)
 
     def __init__(self, length, bins, step, start=0.0, radius=1.0, device=None):
         length, bins = _int(length, "length"), _int(bins, "bins")

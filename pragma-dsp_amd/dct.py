@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import PdspError, check, lib
+from ._device import host_rows
 
 _SWAP = {"backward": "forward", "ortho": "ortho", "forward": "backward"}
 
@@ -26,13 +27,11 @@ def _norm(norm) -> str:
 
 
 def _run(x, type: int, norm: str) -> np.ndarray:
-    a = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
-    if a.ndim not in (1, 2) or a.shape[-1] == 0:
+    a, a2 = host_rows(x, "x")
+    if a.ndim > 2 or a.shape[-1] == 0:
         raise PdspError(_capi.ERR_BAD_ARG, f"x must be 1-D or 2-D with rows along the last axis, got shape {a.shape}")
-    n = a.shape[-1]
-    rows = 1 if a.ndim == 1 else a.shape[0]
     y = np.empty_like(a)
-    check(lib.pdsp_dct_host_f64(_capi.dptr(a), rows, n, int(type), _capi.DCT_NORMS[norm], _capi.dptr(y)))
+    check(lib.pdsp_dct_host_f64(_capi.dptr(a2), a2.shape[0], a2.shape[1], int(type), _capi.DCT_NORMS[norm], _capi.dptr(y)))
     return y
 
 

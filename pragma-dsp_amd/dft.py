@@ -27,7 +27,9 @@ class Dft(ChirpRows):
     """A pdsp_dft on one GPU: the chirp and chirp-filter tables of one length, both precisions."""
 
     _destroy = lib.pdsp_dft_destroy
-    _forward = (lib.pdsp_dft_c2c_f32, lib.pdsp_dft_c2c_f64)
+
+    def _entry(self, sfx):
+        return getattr(lib, "pdsp_dft_c2c_" + sfx)
 
     def __init__(self, length, device=None):
         self._create(lib.pdsp_dft_create, device, integer(length, "length"))

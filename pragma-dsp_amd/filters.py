@@ -19,8 +19,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _device
 from ._capi import PdspError, check, lib
+from ._device import ptr, stream_ptr
 
 MAX_TAPS = 8192  # N/2 of the largest block (16384); longer filters need partitioned convolution
 
@@ -46,35 +47,21 @@ def output_range(length: int, ntaps: int, mode: str) -> tuple[int, int]:
     return off.value, n.value
 
 
-def _rows(t: torch.Tensor, name: str):
-    """(rows, row stride) of a tensor of rows [..., len]: contiguous, or 2-D with unit stride along the row."""
-    if t.dim() == 0:
-        raise PdspError(_capi.ERR_BAD_ARG, f"{name} must have at least one axis")
-    if t.is_contiguous():
-        return int(np.prod(t.shape[:-1], dtype=np.int64)), t.shape[-1]
-    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
-        return t.shape[0], t.stride(0)
-    raise PdspError(_capi.ERR_BAD_ARG, f"{name}: rows at a stride are taken in 2-D tensors only")
-
-
 class FirFilter:
     """One real FIR filter on one GPU: the plan of block size N and the filter's spectrum H (N/2 + 1 bins) on the
     device.  `block` = N (a power of two, 2 * ntaps <= N <= 16384); None picks block_size(ntaps)."""
 
     def __init__(self, taps, device=None, dtype=torch.float32, block=None):
-        if dtype not in (torch.float32, torch.float64):
-            raise PdspError(_capi.ERR_BAD_ARG, f"unsupported dtype {dtype}")
         from .batch import BatchedFft  # the plan object (and its device checks)
 
-        self.dtype = dtype
-        self._sfx = "f32" if dtype == torch.float32 else "f64"
+        self._sfx = _device.suffix(dtype)
         if isinstance(taps, torch.Tensor):
             taps = taps.detach().cpu().numpy()
         taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).reshape(-1))
         self.ntaps = int(taps.size)
         n = block_size(self.ntaps) if block is None else int(block)
         self.plan = BatchedFft(n, device, dtype)
-        self.device = self.plan.device
+        self.dtype, self.device = dtype, self.plan.device
         self.size = n
         self.taps = torch.from_numpy(taps).to(dtype).to(self.device)
         bins = n // 2 + 1
@@ -82,12 +69,10 @@ class FirFilter:
         self.h_im = torch.empty(bins, dtype=dtype, device=self.device)
         with torch.cuda.device(self.device):
             fn = getattr(lib, f"pdsp_fir_spectrum_{self._sfx}")
-            stream = torch.cuda.current_stream(self.device)
-            check(fn(self.plan._h, C.c_void_p(self.taps.data_ptr()), self.ntaps, C.c_void_p(self.h_re.data_ptr()),
-                     C.c_void_p(self.h_im.data_ptr()), C.c_void_p(stream.cuda_stream)))
+            check(fn(self.plan._h, ptr(self.taps), self.ntaps, ptr(self.h_re), ptr(self.h_im), stream_ptr(self.device)))
             # H is written on the stream current at construction; apply() may run on another one
             self._ready = torch.cuda.Event()
-            self._ready.record(stream)
+            self._ready.record(torch.cuda.current_stream(self.device))
 
     def _wait_ready(self):
         torch.cuda.current_stream(self.device).wait_event(self._ready)
@@ -101,23 +86,11 @@ class FirFilter:
     def apply(self, x: torch.Tensor, mode: str = "full", out: torch.Tensor | None = None) -> torch.Tensor:
         """y = x * taps over the last axis of x ([..., len], rows contiguous or a 2-D view with a row stride),
         restricted to the mode's range: shape [..., y_len]."""
-        if x.dtype != self.dtype or not x.is_cuda or x.device != self.device:
-            raise PdspError(_capi.ERR_BAD_ARG, f"input must be a {self.dtype} tensor on {self.device}")
-        length = x.shape[-1] if x.dim() else 0
-        y_off, y_len = output_range(length, self.ntaps, mode)
-        rows, x_stride = _rows(x, "input")
-        if out is None:
-            out = torch.empty(*x.shape[:-1], y_len, dtype=self.dtype, device=self.device)
-        elif out.dtype != self.dtype or out.device != self.device or tuple(out.shape) != (*x.shape[:-1], y_len):
-            raise PdspError(_capi.ERR_BAD_ARG, f"out must be a {self.dtype} tensor of shape {(*x.shape[:-1], y_len)}")
-        _, y_stride = _rows(out, "out")
-        with torch.cuda.device(self.device):
-            self._wait_ready()
-            fn = getattr(lib, f"pdsp_fir_filter_{self._sfx}")
-            check(fn(self.plan._h, rows, C.c_void_p(x.data_ptr()), length, x_stride, C.c_void_p(self.h_re.data_ptr()),
-                     C.c_void_p(self.h_im.data_ptr()), self.ntaps, y_off, y_len, C.c_void_p(out.data_ptr()), y_stride,
-                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-        return out
+        _device.operand(x, "input", self.device, self.dtype, layout="rows")
+        y_off, y_len = output_range(x.shape[-1] if x.dim() else 0, self.ntaps, mode)
+        self._wait_ready()
+        return _device.launch_rows(getattr(lib, f"pdsp_fir_filter_{self._sfx}"), self.plan._h, self, x, out, y_len,
+                                   (ptr(self.h_re), ptr(self.h_im), self.ntaps, y_off, y_len))
 
     __call__ = apply
 
@@ -131,12 +104,10 @@ def firFilter(signal, taps, mode: str = "full") -> np.ndarray:
     """Host f64 form (numpy in, numpy out) through pdsp_fir_filter_host_f64: signal [len] or [batch, len]."""
     if mode not in _capi.FIR_MODES:
         raise PdspError(_capi.ERR_BAD_ARG, f"unknown FIR mode {mode!r}")
-    x = np.ascontiguousarray(np.asarray(signal, dtype=np.float64))
+    x, x2 = _device.host_rows(signal)
     h = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).reshape(-1))
-    one = x.ndim == 1
-    x2 = x.reshape(1, -1) if one else x.reshape(-1, x.shape[-1])
     y_off, y_len = output_range(x2.shape[1], h.size, mode)
     y = np.empty((x2.shape[0], y_len), dtype=np.float64)
     check(lib.pdsp_fir_filter_host_f64(_capi.dptr(x2), x2.shape[0], x2.shape[1], _capi.dptr(h), h.size,
                                        _capi.FIR_MODES[mode], _capi.dptr(y)))
-    return y[0] if one else y.reshape(*x.shape[:-1], y_len)
+    return y.reshape(*x.shape[:-1], y_len)

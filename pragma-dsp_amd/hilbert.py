@@ -15,25 +15,19 @@ import numpy as np
 
 from . import _capi
 from ._capi import PdspError, check, lib
+from ._device import host_rows, integer
 
 
 def _run(x, n, mode: str) -> np.ndarray:
-    a = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
-    if a.ndim not in (1, 2) or a.shape[-1] == 0:
+    a, a2 = host_rows(x, "x")
+    if a.ndim > 2 or a.shape[-1] == 0:
         raise PdspError(_capi.ERR_BAD_ARG, f"x must be 1-D or 2-D with rows along the last axis, got shape {a.shape}")
-    ln = a.shape[-1]
-    if n is None:
-        n = ln
-    elif isinstance(n, bool) or not isinstance(n, (int, np.integer)):
-        raise PdspError(_capi.ERR_BAD_ARG, f"n must be an integer, got {n!r}")
-    n = int(n)
-    if not -2 ** 63 <= n < 2 ** 63:
-        raise PdspError(_capi.ERR_BAD_ARG, f"n must be an integer, got {n!r}")
-    rows = 1 if a.ndim == 1 else a.shape[0]
+    rows, ln = a2.shape
+    n = ln if n is None else integer(n, "n")
     k = 2 if mode == "analytic" else 1
     # a size the library refuses gets no buffer: the library fails before it writes
     y = np.empty(a.shape[:-1] + ((n if 64 <= n <= 16384 else 0) * k,), dtype=np.float64)
-    check(lib.pdsp_hilbert_host_f64(_capi.dptr(a), rows, ln, n, _capi.HILBERT_OUT[mode], _capi.dptr(y)))
+    check(lib.pdsp_hilbert_host_f64(_capi.dptr(a2), rows, ln, n, _capi.HILBERT_OUT[mode], _capi.dptr(y)))
     return y
 
 

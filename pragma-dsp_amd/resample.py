@@ -18,19 +18,16 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _capi
-from ._capi import PdspError, check, lib
-from .filters import _rows
+from . import _capi, _device
+from ._capi import check, lib
+from ._device import host_rows, integer
 
 MAX_RATIO = 8192  # up and down
 MAX_TAPS = 8192   # the FIR module's limit; the default design needs 20 * max(up, down) + 1
 
 
 def _ratio(up, down) -> tuple[int, int]:
-    for name, v in (("up", up), ("down", down)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -2 ** 63 <= int(v) < 2 ** 63:
-            raise PdspError(_capi.ERR_BAD_ARG, f"{name} must be an integer, got {v!r}")
-    return int(up), int(down)
+    return integer(up, "up"), integer(down, "down")
 
 
 def _taps(taps):
@@ -52,39 +49,20 @@ def design_taps(up, down) -> np.ndarray:
     return h
 
 
-class _Handle:
+class _Handle(_device.Handle):
     """A pdsp_resampler on one GPU and what both classes do with it."""
 
+    _destroy = lib.pdsp_resampler_destroy
     _full = 0
 
     def _init(self, device, dtype, create):
-        if dtype not in (torch.float32, torch.float64):
-            raise PdspError(_capi.ERR_BAD_ARG, f"unsupported dtype {dtype}")
-        self.dtype = dtype
-        self._sfx = "f32" if dtype == torch.float32 else "f64"
-        self._h = C.c_void_p()
-        if not torch.cuda.is_available():
-            # argument errors come first, as everywhere: the library checks them without a device
-            probe = C.c_void_p()
-            check(create(-1, C.byref(probe)))
-            lib.pdsp_resampler_destroy(probe)
-            raise PdspError(_capi.ERR_DEVICE, "no HIP device available (the pdsp engine has no CPU fallback)")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        check(create(self.device.index, C.byref(self._h)))
+        self._open(create, device, dtype)
         self.up = int(lib.pdsp_resampler_up(self._h))
         self.down = int(lib.pdsp_resampler_down(self._h))
         self.ntaps = int(lib.pdsp_resampler_ntaps(self._h))
         self.t0 = int(lib.pdsp_resampler_t0(self._h))
         self.taps = np.empty(self.ntaps, dtype=np.float64)
         check(lib.pdsp_resampler_taps(self._h, _capi.dptr(self.taps)))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            lib.pdsp_resampler_destroy(h)
-            self._h = None
 
     def output_len(self, length: int) -> int:
         """Outputs per row of `length` samples."""
@@ -94,23 +72,9 @@ class _Handle:
 
     def apply(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """Rows along the last axis of x ([..., len], contiguous or a 2-D view with a row stride) -> [..., y_len]."""
-        if not isinstance(x, torch.Tensor) or x.dtype != self.dtype or not x.is_cuda or x.device != self.device:
-            raise PdspError(_capi.ERR_BAD_ARG, f"input must be a {self.dtype} tensor on {self.device}")
-        length = x.shape[-1] if x.dim() else 0
-        y_len = self.output_len(length)
-        rows, x_stride = _rows(x, "input")
-        shape = (*x.shape[:-1], y_len)
-        if out is None:
-            out = torch.empty(shape, dtype=self.dtype, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != self.dtype or out.device != self.device
-              or tuple(out.shape) != shape):
-            raise PdspError(_capi.ERR_BAD_ARG, f"out must be a {self.dtype} tensor of shape {shape} on {self.device}")
-        _, y_stride = _rows(out, "out")
-        with torch.cuda.device(self.device):
-            fn = getattr(lib, f"pdsp_upfirdn_{self._sfx}")
-            check(fn(self._h, rows, C.c_void_p(x.data_ptr()), length, x_stride, C.c_void_p(out.data_ptr()), y_len,
-                     y_stride, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-        return out
+        _device.operand(x, "input", self.device, self.dtype, layout="rows")
+        y_len = self.output_len(x.shape[-1] if x.dim() else 0)
+        return _device.launch_rows(getattr(lib, f"pdsp_upfirdn_{self._sfx}"), self._h, self, x, out, y_len, (), (y_len,))
 
     __call__ = apply
 
@@ -149,14 +113,6 @@ def upfirdn(h, x: torch.Tensor, up=1, down=1) -> torch.Tensor:
     return Upfirdn(h, up, down, x.device, x.dtype).apply(x)
 
 
-def _host_rows(signal):
-    x = np.ascontiguousarray(np.asarray(signal, dtype=np.float64))
-    if x.ndim == 0:
-        raise PdspError(_capi.ERR_BAD_ARG, "signal must have at least one axis")
-    rows = int(np.prod(x.shape[:-1], dtype=np.int64))
-    return x, x.reshape(rows, x.shape[-1])
-
-
 def _host_out(x, x2, y_len_of):
     """The output buffer, or none for arguments the library will refuse before it writes."""
     try:
@@ -170,7 +126,7 @@ def resamplePoly(signal, up, down, taps=None) -> np.ndarray:
     """Host f64 form (numpy in, numpy out) through pdsp_resample_poly_host_f64: signal [len] or [..., len]."""
     up, down = _ratio(up, down)
     h = _taps(taps)
-    x, x2 = _host_rows(signal)
+    x, x2 = host_rows(signal)
     y = _host_out(x, x2, lambda n: -(-n * up // down))
     check(lib.pdsp_resample_poly_host_f64(_capi.dptr(x2), x2.shape[0], x2.shape[1], up, down, _capi.dptr(h),
                                           0 if h is None else h.size, _capi.dptr(y)))
@@ -181,7 +137,7 @@ def upfirdnHost(h, x, up=1, down=1) -> np.ndarray:
     """Host f64 form (numpy in, numpy out) through pdsp_upfirdn_host_f64: x [len] or [..., len]."""
     up, down = _ratio(up, down)
     h = _taps(h)
-    x, x2 = _host_rows(x)
+    x, x2 = host_rows(x)
     y = _host_out(x, x2, lambda n: ((n - 1) * up + h.size - 1) // down + 1)
     check(lib.pdsp_upfirdn_host_f64(_capi.dptr(h), h.size, _capi.dptr(x2), x2.shape[0], x2.shape[1], up, down,
                                     _capi.dptr(y)))

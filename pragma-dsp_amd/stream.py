@@ -10,7 +10,6 @@ row, and findPeak runs on the host over the f64-promoted amplitudes exactly as t
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Iterable, Iterator
 
 import numpy as np
@@ -18,6 +17,7 @@ import torch
 
 from . import _capi
 from ._capi import PdspError, check, dptr, lib
+from ._device import resolve_device
 from .batch import BatchedFft, _ptr, _stream_ptr
 from .core import as_f64, isPowerOfTwo, js_num, nextPowerOfTwo
 from .fourier import binFrequencies
@@ -51,15 +51,13 @@ class SpectrumStream:
             raise PdspError(_capi.ERR_SAMPLE_RATE, f"Sample rate must be positive, got {js_num(self.sample_rate)}")
         if batch_frames < 1:
             raise ValueError("batch_frames must be >= 1")
-        if not torch.cuda.is_available():
-            raise PdspError(_capi.ERR_DEVICE, "no HIP device available (the pdsp engine has no CPU fallback)")
+        self.device = resolve_device(device)
         self.batch_frames = int(batch_frames)
         # same arithmetic as spectrum(): the host precision (pdsp_set_host_precision), f64 by default;
         # per size it falls to f32 where the f64 tables do not reach, exactly as
         # pdsp_spectrum_batch_host_f64 does (_dtype_for)
         self.dtype = torch.float64 if lib.pdsp_set_host_precision(0) == 64 else torch.float32
         self.slot_bytes = int(opts.get("slotBytes", 1 << 30))  # cap on one slot's pinned input staging
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self._plans: dict[int, BatchedFft] = {}     # Map<size, FFT>
         self._freqs: dict[int, np.ndarray] = {}
         self._slots: dict[int, list[_Slot]] = {}    # two staging slots per size

@@ -24,10 +24,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, _device
 from ._capi import PdspError, check, lib
-from .filters import _rows
-from .resample import _host_rows
+from ._device import host_rows, integer
 
 MAX_TAPS = 32
 
@@ -42,12 +41,6 @@ def _wavelet(wavelet):
     return None, h, h.size
 
 
-def _levels(levels) -> int:
-    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not -2 ** 31 <= int(levels) < 2 ** 31:
-        raise PdspError(_capi.ERR_BAD_ARG, f"levels must be an integer, got {levels!r}")
-    return int(levels)
-
-
 def wavelet_taps(name: str) -> np.ndarray:
     """The scaling filter of a built-in wavelet: "haar" (= "db1"), "db2" ... "db10" (extremal phase, sum sqrt 2)."""
     if not isinstance(name, str):
@@ -59,59 +52,29 @@ def wavelet_taps(name: str) -> np.ndarray:
     return h
 
 
-class Dwt:
+class Dwt(_device.Handle):
     """A pdsp_dwt on one GPU: `levels` levels of one orthogonal wavelet over rows along the last axis."""
 
+    _destroy = lib.pdsp_dwt_destroy
+
     def __init__(self, wavelet, levels, device=None, dtype=torch.float32):
-        if dtype not in (torch.float32, torch.float64):
-            raise PdspError(_capi.ERR_BAD_ARG, f"unsupported dtype {dtype}")
+        _device.suffix(dtype)
         name, h, ntaps = _wavelet(wavelet)
-        levels = _levels(levels)
-        self.dtype = dtype
-        self._sfx = "f32" if dtype == torch.float32 else "f64"
-        self._h = C.c_void_p()
-        if not torch.cuda.is_available():
-            # argument errors come first, as everywhere: the library checks them without a device
-            probe = C.c_void_p()
-            check(lib.pdsp_dwt_create(-1, name, _capi.dptr(h), ntaps, levels, C.byref(probe)))
-            lib.pdsp_dwt_destroy(probe)
-            raise PdspError(_capi.ERR_DEVICE, "no HIP device available (the pdsp engine has no CPU fallback)")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        check(lib.pdsp_dwt_create(self.device.index, name, _capi.dptr(h), ntaps, levels, C.byref(self._h)))
+        levels = integer(levels, "levels", 32)
+        self._open(lambda dev, out: lib.pdsp_dwt_create(dev, name, _capi.dptr(h), ntaps, levels, out), device, dtype)
         self.levels = int(lib.pdsp_dwt_levels(self._h))
         self.ntaps = int(lib.pdsp_dwt_ntaps(self._h))
         self.taps = np.empty(self.ntaps, dtype=np.float64)
         check(lib.pdsp_dwt_taps(self._h, _capi.dptr(self.taps)))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            lib.pdsp_dwt_destroy(h)
-            self._h = None
 
     def max_levels(self, length: int) -> int:
         """The deepest forward transform of rows of `length` values in this precision (0: none)."""
         return int(lib.pdsp_dwt_max_levels(self.ntaps, int(length), 4 if self.dtype == torch.float32 else 8))
 
     def _run(self, direction: str, x: torch.Tensor, out: torch.Tensor | None) -> torch.Tensor:
-        if not isinstance(x, torch.Tensor) or x.dtype != self.dtype or not x.is_cuda or x.device != self.device:
-            raise PdspError(_capi.ERR_BAD_ARG, f"input must be a {self.dtype} tensor on {self.device}")
-        length = x.shape[-1] if x.dim() else 0
-        rows, x_stride = _rows(x, "input")
-        shape = tuple(x.shape)
-        if out is None:
-            out = torch.empty(shape, dtype=self.dtype, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != self.dtype or out.device != self.device
-              or tuple(out.shape) != shape):
-            raise PdspError(_capi.ERR_BAD_ARG, f"out must be a {self.dtype} tensor of shape {shape} on {self.device}")
-        _, y_stride = _rows(out, "out")
-        with torch.cuda.device(self.device):
-            fn = getattr(lib, f"pdsp_dwt_{direction}_{self._sfx}")
-            check(fn(self._h, rows, C.c_void_p(x.data_ptr()), length, x_stride, C.c_void_p(out.data_ptr()), y_stride,
-                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-        return out
+        _device.operand(x, "input", self.device, self.dtype, layout="rows")
+        return _device.launch_rows(getattr(lib, f"pdsp_dwt_{direction}_{self._sfx}"), self._h, self, x, out,
+                                   x.shape[-1] if x.dim() else 0)
 
     def forward(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """Rows of samples ([..., n], contiguous or a 2-D view with a row stride) -> rows of n coefficients,
@@ -150,8 +113,8 @@ def waverec(c: torch.Tensor, wavelet, levels) -> torch.Tensor:
 
 def _host(fn, signal, wavelet, levels) -> np.ndarray:
     name, h, ntaps = _wavelet(wavelet)
-    levels = _levels(levels)
-    x, x2 = _host_rows(signal)
+    levels = integer(levels, "levels", 32)
+    x, x2 = host_rows(signal)
     y = np.empty_like(x2)
     check(fn(_capi.dptr(x2), x2.shape[0], x2.shape[1], name, _capi.dptr(h), ntaps, levels, _capi.dptr(y)))
     return y.reshape(x.shape)
