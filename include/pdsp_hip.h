@@ -285,7 +285,10 @@ PDSP_API int pdsp_spectrum_peaks_f32(const pdsp_plan *plan, long long batch,
 
 /* ---- the same device-pointer family in f64 ------------------------------ */
 /* Identical contracts with double rows, N <= 2^26 (PDSP_ERR_UNSUPPORTED_SIZE beyond).
- * Per bin, 2.3e-16 * log2 N of the row's rms at most (measured against long-double references). */
+ * Per bin, 2.3e-16 * log2 N of the row's rms at most (measured against long-double references).
+ * pdsp_fft_forward_real_f64 at N = 16384 runs one kernel variant from 8 rows up and another below, so there the variant,
+ * and with it the last bits of a row, depend on the batch (pdsp_dev_transform_path_f64 in pdsp_hip_dev.h names it); the
+ * host entry points below choose by size alone, and a row's bits never depend on its batch. */
 PDSP_API int pdsp_fft_forward_real_f64(const pdsp_plan *plan, long long batch,
                                        const double *re_in, double *re_out, double *im_out,
                                        pdsp_stream stream);
@@ -318,7 +321,8 @@ PDSP_API int pdsp_spectrum_f64(const pdsp_plan *plan, long long batch,
 /* Radix2Fft.transform, src/core/fft.ts:89-151, for `batch` rows.  im_in may be
  * NULL (= forward(real)).  in_len is the caller's row length and must equal N
  * (PDSP_ERR_INPUT_LENGTH otherwise, message as fft.ts:95-104).  Computes on the
- * device in the precision pdsp_set_host_precision() selects (f64 at the boundary either way). */
+ * device in the precision pdsp_set_host_precision() selects (f64 at the boundary either way).
+ * Row b equals the one-row call on row b bit for bit, at every batch and however the call is cut into chunks. */
 PDSP_API int pdsp_fft_transform_host_f64(pdsp_plan *plan, long long batch, long long in_len,
                                          const double *re_in, const double *im_in,
                                          double *re_out, double *im_out, int inverse);

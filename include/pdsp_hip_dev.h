@@ -43,7 +43,8 @@ PDSP_API int pdsp_set_fused_window(int enabled);
 PDSP_API int pdsp_set_twopass(int enabled);
 
 /* 1 (default): f64 Radix2Fft.forward rows (real input, src/core/fft.ts:77-79) of N = 8192, and of N = 16384 from 8
- * rows up, run as ONE N/2-point packed-real transform per row + the split to X[k], X[k + N/2] (fft_real_kernel);
+ * rows up (the device forms; the host forms: at every row count, so that a row's bits never depend on its batch),
+ * run as ONE N/2-point packed-real transform per row + the split to X[k], X[k + N/2] (fft_real_kernel);
  * 0: as the complex kernel of their size on (x, 0) (fft_stockham_kernel with LoadReal; N = 16384: the four-step
  * path).  Same results within rounding.  Other sizes and f32 real rows always take the complex kernels
  * (DESIGN 4.1c). */
@@ -137,6 +138,17 @@ PDSP_API int pdsp_dev_spectrum_path_f64(const pdsp_plan *plan, long long batch, 
                                         long long frame_len, long long frame_stride, const double *window, int sides,
                                         const double *amp_out, const double *phase_out, const int32_t *peak_idx_out,
                                         const pdsp_peak32 *peaks_out, double sample_rate, int info[PDSP_DEV_PATH_INFO]);
+
+/* How a batched host call would be cut under the current PDSP_HOST_THREADS (read at the call, like the calls do):
+ * pdsp_fft_transform_host_f64 / _rows_host_f64 of `batch` rows on this plan, or pdsp_spectrum_batch_host_f64 /
+ * _rows_host_f64 / _rows_host_f32in of `batch` non-empty frames at this plan's size, in host precision 32 or 64 (a size
+ * beyond the f64 tables runs in f32, as in the calls).  info[0] = rows per chunk -- the last chunk holds the
+ * remainder -- and info[1] = workers; both 0 when the call keeps the one-shot sequence (as it also does, whatever this
+ * says, when its planes overlap in host memory).  The calls ask the same function.  Launches nothing; needs no
+ * device beyond the plan's. */
+PDSP_API int pdsp_dev_host_transform_chunks(const pdsp_plan *plan, long long batch, int precision, long long info[2]);
+PDSP_API int pdsp_dev_host_spectrum_chunks(const pdsp_plan *plan, long long batch, int sides, int precision,
+                                           long long info[2]);
 
 #ifdef __cplusplus
 }

@@ -193,6 +193,8 @@ def _load() -> C.CDLL:
         "pdsp_dev_transform_path_f64": ([vp, ll, vp, vp, vp, vp, i32, C.POINTER(i32)], i32),
         "pdsp_dev_spectrum_path_f32": ([vp, ll, vp, ll, ll, vp, i32, vp, vp, vp, vp, C.c_double, C.POINTER(i32)], i32),
         "pdsp_dev_spectrum_path_f64": ([vp, ll, vp, ll, ll, vp, i32, vp, vp, vp, vp, C.c_double, C.POINTER(i32)], i32),
+        "pdsp_dev_host_transform_chunks": ([vp, ll, i32, C.POINTER(ll)], i32),
+        "pdsp_dev_host_spectrum_chunks": ([vp, ll, i32, i32, C.POINTER(ll)], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

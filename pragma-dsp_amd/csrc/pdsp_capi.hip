@@ -458,7 +458,11 @@ int require_device() {
 // slot and one stream and draw chunks from a shared counter: fill the slot, H2D, the same kernels the one-shot path
 // launches, D2H, wait for the stream, unstage (+ findPeak).  Inside a worker the steps stay in order; across workers
 // staging, both PCIe directions and the kernels overlap.  Row b of the result is the one-shot result of row b bit
-// for bit (the kernels work row by row and the variant does not depend on the row count).  A worker keeps one
+// for bit, and the one-row call's on row b: the kernels work row by row, and the host forms choose the variant from
+// the plan and the call's kind alone (run_complex with by_size; pick_spectrum never looks at the row count), so a
+// chunk of any length, its shorter tail and a one-row call all run the same kernel on a row.  (Until the host forms
+// passed by_size, f64 real rows of N = 16384 took fft_real_kernel from 8 rows per chunk up and the four-step path
+// below: the bits depended on PDSP_HOST_THREADS, the core count and the batch.)  A worker keeps one
 // chunk on the card while it fills the next (two slots and streams per worker).
 // PDSP_HOST_THREADS sets K (1 = the one-shot sequence; default: half the cores this process may run on, 2 ... 6).
 constexpr size_t kChunkInBytes = (size_t)2 << 20;
@@ -488,6 +492,37 @@ int host_workers(bool multipass = false) {
   }
   if (multipass && v > 2) v = 2;
   return (int)(v > 16 ? 16 : v);
+}
+
+// How a batched host call is cut: rows per chunk and workers, or chunked = false for the one-shot sequence (which
+// planes that overlap in host memory keep whatever this says).  pdsp_dev_host_*_chunks report it.
+struct HostCut {
+  bool chunked = false;
+  long long per_chunk = 0;
+  int workers = 0;
+};
+// pdsp_fft_transform_*host_f64 in precision T.  (Two planes' worth whether or not there is an imaginary input: the
+// slot -- re | im | out re | out im -- stays at 2 x kChunkInBytes, so 2 slots x 6 workers fit the staging a plan
+// keeps between calls.)
+template <typename T>
+HostCut transform_cut(const pdsp_plan *plan, long long batch) {
+  const size_t row_bytes = (size_t)plan->n * sizeof(T), cnt = (size_t)batch * (size_t)plan->n;
+  HostCut c;
+  c.workers = host_workers(tables<T>(plan).log2n1 > 0);
+  c.per_chunk = (long long)(chunk_in_bytes(2 * cnt * sizeof(T), c.workers) / (2 * row_bytes));
+  c.chunked = c.workers >= 2 && c.per_chunk >= 1 && batch >= 2 * c.per_chunk && 4 * cnt * sizeof(T) >= kChunkedMinBytes;
+  return c;
+}
+// pdsp_spectrum_*host_* on frames of len > 0 samples in precision T
+template <typename T>
+HostCut spectrum_cut(const pdsp_plan *plan, long long batch, long long bins) {
+  const size_t frame_bytes = (size_t)plan->n * sizeof(T);
+  HostCut c;
+  c.workers = host_workers(tables<T>(plan).log2n1 > 0 && !tables<T>(plan).tw_half);  // packed-real frames: one pass
+  c.per_chunk = (long long)(chunk_in_bytes((size_t)batch * frame_bytes, c.workers) / frame_bytes);
+  c.chunked = c.workers >= 2 && c.per_chunk >= 1 && batch >= 2 * c.per_chunk &&
+              (size_t)batch * (size_t)(plan->n + 2 * bins) * sizeof(T) >= kChunkedMinBytes;
+  return c;
 }
 
 inline bool host_ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
@@ -689,11 +724,10 @@ int transform_host(pdsp_plan *plan, long long batch, const double *re_in, const 
   {
     // many rows: chunks on several workers (run_chunked); planes that overlap each other in host memory keep the
     // one-shot sequence, which has read every input before it writes any output
-    const size_t row_bytes = n * sizeof(T), out_bytes = cnt * sizeof(double), in_row_bytes = n * sizeof(double);
-    // (two planes' worth whether or not there is an imaginary input: the slot -- re | im | out re | out im -- stays
-    // at 2 x kChunkInBytes, so 2 slots x 6 workers fit the staging a plan keeps between calls)
-    const int workers = host_workers(tables<T>(plan).log2n1 > 0);
-    const long long per_chunk = (long long)(chunk_in_bytes(2 * cnt * sizeof(T), workers) / (2 * row_bytes));
+    const size_t out_bytes = cnt * sizeof(double), in_row_bytes = n * sizeof(double);
+    const HostCut cut = transform_cut<T>(plan, batch);
+    const int workers = cut.workers;
+    const long long per_chunk = cut.per_chunk;
     bool overlap = false;
     if (re_rows || im_rows) {
       for (long long r = 0; r < batch && !overlap; ++r)
@@ -705,7 +739,7 @@ int transform_host(pdsp_plan *plan, long long batch, const double *re_in, const 
       overlap = host_ranges_overlap(re_in, out_bytes, re_out, out_bytes) || host_ranges_overlap(re_in, out_bytes, im_out, out_bytes) ||
                 host_ranges_overlap(im_in, out_bytes, re_out, out_bytes) || host_ranges_overlap(im_in, out_bytes, im_out, out_bytes);
     }
-    if (workers >= 2 && per_chunk >= 1 && batch >= 2 * per_chunk && 4 * cnt * sizeof(T) >= kChunkedMinBytes && !overlap) {
+    if (cut.chunked && !overlap) {
       const size_t slot = 4 * (size_t)per_chunk * n;  // elements: re | im | out re | out im
       const int k = (long long)workers < (batch + per_chunk - 1) / per_chunk ? workers : (int)((batch + per_chunk - 1) / per_chunk);
       if (int rc = ensure_stage(plan, (size_t)kSlotsPerWorker * k * slot * sizeof(T))) return rc;
@@ -717,8 +751,9 @@ int transform_host(pdsp_plan *plan, long long batch, const double *re_in, const 
             stage_in(h, h + c, job.first, job.count, true);
             PDSP_HIP_TRY(hipMemcpyAsync(d, h, (has_im ? 2 : 1) * c * sizeof(T), hipMemcpyHostToDevice, job.stream));
             int rc;
-            if (inverse) rc = run_complex<T>(plan, job.count, d + c, d, d + 3 * c, d + 2 * c, T(1) / (T)plan->n, job.stream);
-            else rc = run_complex<T>(plan, job.count, d, has_im ? d + c : nullptr, d + 2 * c, d + 3 * c, T(1), job.stream);
+            // by_size: a chunk's row count must not choose the kernel (see above kChunkInBytes)
+            if (inverse) rc = run_complex<T>(plan, job.count, d + c, d, d + 3 * c, d + 2 * c, T(1) / (T)plan->n, job.stream, true);
+            else rc = run_complex<T>(plan, job.count, d, has_im ? d + c : nullptr, d + 2 * c, d + 3 * c, T(1), job.stream, true);
             if (rc) return rc;
             PDSP_HIP_TRY(hipMemcpyAsync(h + 2 * c, d + 2 * c, 2 * c * sizeof(T), hipMemcpyDeviceToHost, job.stream));
             return PDSP_OK;
@@ -746,8 +781,8 @@ int transform_host(pdsp_plan *plan, long long batch, const double *re_in, const 
   int rc;
   // inverse: conj(FFT(conj(z))) == swap(FFT(swap(z))) -- the conjugated-twiddle sweep of fft.ts:122
   // is the forward kernel with the planes exchanged on the way in and out; 1/N rides on the store
-  if (inverse) rc = run_complex<T>(plan, batch, d_im, d_re, d_oim, d_ore, T(1) / (T)plan->n, s);
-  else rc = run_complex<T>(plan, batch, d_re, has_im ? d_im : nullptr, d_ore, d_oim, T(1), s);
+  if (inverse) rc = run_complex<T>(plan, batch, d_im, d_re, d_oim, d_ore, T(1) / (T)plan->n, s, true);
+  else rc = run_complex<T>(plan, batch, d_re, has_im ? d_im : nullptr, d_ore, d_oim, T(1), s, true);
   if (rc) return rc;
   if (!z) PDSP_HIP_TRY(hipMemcpyAsync(h_ore, d_ore, 2 * cnt * sizeof(T), hipMemcpyDeviceToHost, s));
   PDSP_HIP_TRY(hipStreamSynchronize(s));
@@ -845,12 +880,12 @@ int spectrum_host_t(pdsp_plan *plan, const FrameSource &in, int window, int side
   {
     // many frames: chunks on several workers (run_chunked)
     const size_t frame_bytes = (size_t)n * sizeof(T);
-    const int workers = host_workers(tables<T>(plan).log2n1 > 0 && !tables<T>(plan).tw_half);  // packed-real frames: one pass
-    const long long per_chunk = (long long)(chunk_in_bytes((size_t)batch * frame_bytes, workers) / frame_bytes);
+    const HostCut cut = spectrum_cut<T>(plan, batch, bins);
+    const int workers = cut.workers;
+    const long long per_chunk = cut.per_chunk;
     const size_t out_b = (size_t)batch * (size_t)bins * sizeof(double);
     const bool overlap = len > 0 && (in.overlaps(amp_out, out_b, batch) || in.overlaps(phase_out, out_b, batch));
-    if (workers >= 2 && per_chunk >= 1 && batch >= 2 * per_chunk && len > 0 &&
-        (size_t)batch * (size_t)(n + 2 * bins) * sizeof(T) >= kChunkedMinBytes && !overlap) {
+    if (cut.chunked && len > 0 && !overlap) {
       const T *d_window = nullptr;
       if (n != 1 && window != PDSP_WIN_RECT) {
         if (int rc = plan_window<T>(plan, window, &d_window)) return rc;  // built once, before the workers read it
@@ -2248,6 +2283,31 @@ int pdsp_dev_spectrum_path_f64(const pdsp_plan *plan, long long batch, const dou
                                double sample_rate, int info[PDSP_DEV_PATH_INFO]) {
   return spectrum_path<double>(plan, batch, frames, frame_len, frame_stride, window, sides, amp_out, phase_out,
                                peak_idx_out, peaks_out, sample_rate, info);
+}
+
+// The host calls' own rule (transform_cut / spectrum_cut) in the precision the call would run in
+static int host_cut_out(const pdsp_plan *plan, long long batch, int precision, long long info[2], long long bins) {
+  if (int rc = check_plan_batch(plan, batch)) return rc;
+  if (!info) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  if (precision != 32 && precision != 64) return fail(PDSP_ERR_BAD_ARG, "precision must be 32 or 64, got %d", precision);
+  const bool f64 = precision == 64 && (plan->t64.tw || (bins && plan->t64.tw_half));
+  HostCut c;
+  if (batch > 0) {
+    if (bins) c = f64 ? spectrum_cut<double>(plan, batch, bins) : spectrum_cut<float>(plan, batch, bins);
+    else c = f64 ? transform_cut<double>(plan, batch) : transform_cut<float>(plan, batch);
+  }
+  const long long nchunks = c.chunked ? (batch + c.per_chunk - 1) / c.per_chunk : 0;
+  info[0] = c.chunked ? c.per_chunk : 0;
+  info[1] = c.chunked ? (c.workers < nchunks ? c.workers : nchunks) : 0;
+  return PDSP_OK;
+}
+int pdsp_dev_host_transform_chunks(const pdsp_plan *plan, long long batch, int precision, long long info[2]) {
+  return host_cut_out(plan, batch, precision, info, 0);
+}
+int pdsp_dev_host_spectrum_chunks(const pdsp_plan *plan, long long batch, int sides, int precision, long long info[2]) {
+  if (sides != PDSP_SIDES_ONE && sides != PDSP_SIDES_TWO) return fail(PDSP_ERR_BAD_ARG, "bad sides %d", sides);
+  if (!plan) return fail(PDSP_ERR_BAD_ARG, "plan is null");
+  return host_cut_out(plan, batch, precision, info, sides == PDSP_SIDES_ONE ? plan->n / 2 + 1 : plan->n);
 }
 
 int pdsp_dev_upfirdn_tile(long long up, long long down, long long ntaps, long long y_len, int elem_bytes,

@@ -151,7 +151,7 @@ void pick_tiles(const Tables<T> &t, int np, const int *l, int first, Pick &p) {
 
 template <typename T>
 Pick pick_transform(const pdsp_plan *plan, long long batch, const T *re_in, const T *im_in, const T *re_out,
-                    const T *im_out) {
+                    const T *im_out, bool by_size = false) {
   const Tables<T> &t = tables<T>(plan);
   const int L = plan->log2n;
   Pick p;
@@ -169,7 +169,10 @@ Pick pick_transform(const pdsp_plan *plan, long long batch, const T *re_in, cons
   // the same kernel measured +1 ... +9 % on one box and -9 ... +2 % on another (and 3-7 % slower for one frame): not
   // robust, not dispatched, not built.  In f32 it measured 0.98 ... 1.01 of the complex kernels: not built either.
   // Rows aligned to a sample pair.
-  if (sizeof(T) == 8 && !im_in && g_real_packed && (L == 13 || (L == 14 && batch >= 8)) && t.tw_half && t.twr &&
+  // by_size: the host forms (transform_host), which promise that a row's bits depend neither on the rows that travel
+  // with it nor on how the call is cut into chunks -- there N = 16384 runs this kernel at every row count (DESIGN.md
+  // 4.1d has the times); the batch threshold is the device forms' alone.
+  if (sizeof(T) == 8 && !im_in && g_real_packed && (L == 13 || (L == 14 && (by_size || batch >= 8))) && t.tw_half && t.twr &&
       aligned(2 * sizeof(T), re_in)) {
     p.path = kRealPacked;
     return p;
@@ -708,10 +711,10 @@ int transform_path(const pdsp_plan *plan, long long batch, const T *re_in, const
 
 template <typename T>
 int run_complex(const pdsp_plan *plan, long long batch, const T *re_in, const T *im_in, T *re_out, T *im_out, T scale,
-                hipStream_t s) {
+                hipStream_t s, bool by_size) {
   if (int rc = check_transform<T>(plan, batch, re_in, re_out, im_out)) return rc;
   if (batch == 0) return PDSP_OK;
-  const Pick p = pick_transform<T>(plan, batch, re_in, im_in, re_out, im_out);
+  const Pick p = pick_transform<T>(plan, batch, re_in, im_in, re_out, im_out, by_size);
   const Tables<T> &t = tables<T>(plan);
   DeviceGuard g(plan->device);
   PDSP_HIP_TRY(g.err);

@@ -245,9 +245,11 @@ inline int check_plan_batch(const pdsp_plan *plan, long long batch) {
 
 // ---- kernel dispatchers: defined in pdsp_dispatch.inc, instantiated for float / double in the kernel units -------
 // Rows of planar complex points -> rows (forward; the callers swap planes and pass 1/N for the inverse).
+// by_size: the kernel variant is chosen from the plan and the call's kind alone, never from `batch` (the host forms,
+// whose `batch` is whatever piece of the caller's rows a chunk holds).
 template <typename T>
 int run_complex(const pdsp_plan *plan, long long batch, const T *re_in, const T *im_in, T *re_out, T *im_out, T scale,
-                hipStream_t s);
+                hipStream_t s, bool by_size = false);
 template <typename T>
 int run_interleaved(const pdsp_plan *plan, long long batch, const T *in, T *out, bool inverse, hipStream_t s);
 // The batched body of spectrum() (pdsp_spectrum_f32 / _f64 / pdsp_spectrum_peaks_f32).

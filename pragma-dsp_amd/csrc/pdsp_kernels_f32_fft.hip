@@ -4,7 +4,7 @@
 
 namespace pdsp_host {
 template int run_complex<float>(const pdsp_plan *, long long, const float *, const float *, float *, float *, float,
-                                hipStream_t);
+                                hipStream_t, bool);
 template int transform_path<float>(const pdsp_plan *, long long, const float *, const float *, const float *, const float *,
                                    int *);
 template int run_interleaved<float>(const pdsp_plan *, long long, const float *, float *, bool, hipStream_t);

@@ -4,7 +4,7 @@
 
 namespace pdsp_host {
 template int run_complex<double>(const pdsp_plan *, long long, const double *, const double *, double *, double *, double,
-                                 hipStream_t);
+                                 hipStream_t, bool);
 template int run_interleaved<double>(const pdsp_plan *, long long, const double *, double *, bool, hipStream_t);
 template int spectrum_impl<double>(const pdsp_plan *, long long, const double *, long long, long long, const double *, int,
                                    double *, double *, int32_t *, pdsp_peak32 *, double, hipStream_t);

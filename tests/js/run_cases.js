@@ -124,8 +124,9 @@ const results = cases.map((c) => {
       }
       case 'transformBatch': {
         // forwardBatch / forwardComplexBatch / inverseBatch: element i equals the one-row call on inputs[i] exactly
-        // (c.n <= 8192: the kernel does not depend on the row count), also when the call is large enough to be cut
-        // into chunks on the library's workers (c.count rows generated here)
+        // (on the host boundary the kernel never depends on the row count: at N = 16384 nine real rows are above the
+        // device forms' 8-row threshold and forward() is one row), also when the call is large enough to be cut into
+        // chunks on the library's workers (c.count rows generated here)
         const fft = new p.fourier.FFT(c.n);
         let seed = 4242;
         const rnd = () => { seed = (seed * 1103515245 + 12345) % 2147483648; return seed / 2147483648 - 0.5; };

@@ -45,7 +45,8 @@ def test_header_and_ctypes_symbols_agree(pdsp):
         "pdsp_set_split16k", "pdsp_set_staged_small", "pdsp_set_fused_window", "pdsp_set_twopass",
         "pdsp_set_real_packed", "pdsp_set_istft_chunk_frames", "pdsp_set_upfirdn_tile", "pdsp_dev_upfirdn_tile",
         "pdsp_set_dwt_tile", "pdsp_dev_dwt_tile", "pdsp_dev_complex_op_vec4", "pdsp_dev_transform_path_f32",
-        "pdsp_dev_transform_path_f64", "pdsp_dev_spectrum_path_f32", "pdsp_dev_spectrum_path_f64"])
+        "pdsp_dev_transform_path_f64", "pdsp_dev_spectrum_path_f32", "pdsp_dev_spectrum_path_f64",
+        "pdsp_dev_host_transform_chunks", "pdsp_dev_host_spectrum_chunks"])
     assert not [s for s in header_symbols() if "_path_" in s]
     raw = C.CDLL(pdsp.LIB_PATH)
     for s in dev:

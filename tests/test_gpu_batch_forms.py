@@ -28,6 +28,19 @@ def test_spectrum_batch_equals_spectrum_per_frame_and_oracle(oracle_mod):
             assert np.abs(g.amplitude - w["amplitude"]).max() <= 1e-10
             if opts.get("sides", "one") == "one":
                 assert g.peak.index == w["peak"]["index"]
+    # one run of N = 16384 frames (f64 frames of this size are one 8192-point packed transform, batched or alone)
+    t = np.arange(16384)
+    frames16 = [np.sin(2 * np.pi * (700 + i) * t / 16384) + 0.05 * rng.standard_normal(16384) for i in range(9)]
+    opts = {"sampleRate": 48000, "window": "hamming"}
+    got = pd.spectrumBatch(frames16, opts)
+    assert len(got) == len(frames16)
+    for i, (f, g) in enumerate(zip(frames16, got)):
+        one = pd.spectrum(f, opts)
+        assert np.array_equal(g.frequencies, one.frequencies) and np.array_equal(g.amplitude, one.amplitude)
+        assert np.array_equal(g.phase, one.phase) and g.peak == one.peak
+        if i in (0, 4, 8):
+            w = oracle_mod.spectrum(f, sample_rate=48000, fft_size=None, window="hamming", sides="one")
+            assert np.abs(g.amplitude - w["amplitude"]).max() <= 1e-10 and g.peak.index == w["peak"]["index"]
     assert pd.spectrumBatch([], {"sampleRate": 48000}) == []
     with pytest.raises(pd.PdspError, match="FFT size must be power of two, got 12"):
         pd.spectrumBatch(frames[:2], {"fftSize": 12})
@@ -35,7 +48,9 @@ def test_spectrum_batch_equals_spectrum_per_frame_and_oracle(oracle_mod):
         pd.spectrumBatch(frames[:2], {"sampleRate": 0})
 
 
-@pytest.mark.parametrize("n,count", [(8, 3), (1024, 9), (4096, 300)])   # 300 x 4096: the chunked host path
+# 300 x 4096: the chunked host path.  N = 16384: nine real rows are above the device forms' 8-row threshold for
+# fft_real_kernel and each forward() is one row, below it; 20 rows are cut into chunks of 5; 32768: multi-pass rows
+@pytest.mark.parametrize("n,count", [(8, 3), (1024, 9), (4096, 300), (16384, 9), (16384, 20), (32768, 5)])
 def test_transform_batches_equal_the_one_row_calls_and_oracle(oracle_mod, n, count):
     import pragma_dsp_amd as pd
     rng = np.random.default_rng(n)

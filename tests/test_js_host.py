@@ -104,7 +104,13 @@ def test_js_dropin_parity(tmp_path, oracle_mod, reallife, manifest):
     # as one device batch): a small call and one large enough for the library's chunked path (300 rows of 8192)
     typed_cases += [{"op": "transformBatch", "n": 1024, "count": 9}, {"op": "transformBatch", "n": 8192, "count": 300}]
     typed_cases.append({"op": "spectrumBatchOverlap", "n": 1024, "options": {"sampleRate": 48000, "window": "hann"}})
+    # nine real rows of N = 16384: more than the device forms' 8-row threshold for their packed-real kernel, against
+    # forward() on one row each -- on the host boundary the kernel is chosen by size alone
+    typed_cases.append({"op": "transformBatch", "n": 16384, "count": 9})
     tres = run_cases(typed_cases, tmp_path)
+    tb16 = tres[7]
+    assert tb16["same"] is True and tb16["count"] == 9 and tb16["roundTrip"] < 1e-12 and tb16["empty"] == 0
+    assert tb16["threw"] == "FFT input length 3 != size 16384"
     assert tres[6] == {"same": True, "count": 21}   # (6 n - n) / (n / 4) + 1 overlapping views
     for tb in tres[4:6]:
         assert tb["same"] is True and tb["roundTrip"] < 1e-12 and tb["empty"] == 0
