@@ -716,6 +716,55 @@ PDSP_API int pdsp_dwt_forward_host_f64(const double *x, long long batch, long lo
 PDSP_API int pdsp_dwt_inverse_host_f64(const double *c, long long batch, long long len, const char *name_or_null,
                                        const double *taps_or_null, long long ntaps, int levels, double *x);
 
+/* ---- number-theoretic transform (NTT) and exact integer convolution over GF(2^64 - 2^32 + 1), uint64 ---------- */
+/* Field: GF(p), p = 2^64 - 2^32 + 1 = 18446744069414584321.  An element is a uint64_t.  An input may be any 64-bit
+ * pattern and is taken mod p on load (one conditional subtraction: 2^64 < 2 p); every output is canonical, in [0, p).
+ * Root: omega_N = 7^((p - 1) / N) mod p for N = 2^k, k <= 32 (7 generates the multiplicative group).  omega_4 = 2^48
+ * and omega_64 = 2^39: 2 has order 192 and 2^96 = -1.
+ * Transforms, natural order in and out:
+ *   forward  X[k] = sum_n x[n] omega_N^(n k) mod p
+ *   inverse  x[n] = N^-1 sum_k X[k] omega_N^(-n k) mod p
+ * Convolution: c[i] = sum_{j + l = i (mod N)} a[j] b[l] mod p for i < out_len <= N, the rows a (a_len <= N values) and
+ * b (b_len <= N) zero-padded to N: the linear product when a_len + b_len - 1 <= N, the cyclic one otherwise.
+ * b_stride == 0 shares one b row among all rows of a.  One launch: both forward transforms, the point-wise product and
+ * the inverse run in one kernel.
+ * Nothing is rounded: a result is the same 64 bits on every path, whatever the batch, the stride or the form.
+ * Sizes: N = 2^k, 64 <= N <= 16384; not a power of two: PDSP_ERR_SIZE_NOT_POW2, another power of two:
+ * PDSP_ERR_UNSUPPORTED_SIZE.
+ * Checked before any device work (PDSP_ERR_BAD_ARG): null handle or buffers, batch < 0, lengths outside 1 ... N,
+ * strides shorter than the row (b_stride 0 excepted), extents that overflow 64 bits, a grid of 2^31 workgroups, and any
+ * overlap of the output with an input other than out == in (conv: out == a) with equal strides -- a thread stores the
+ * positions it loaded, so that call is exact in place. */
+typedef struct pdsp_ntt pdsp_ntt;
+/* device < 0: arguments are checked without a device, the object binds to the device current at its first call */
+PDSP_API int pdsp_ntt_create(long long n, int device, pdsp_ntt **out);
+PDSP_API int pdsp_ntt_destroy(pdsp_ntt *h);
+PDSP_API long long pdsp_ntt_size(const pdsp_ntt *h);
+/* `batch` rows of N values at in_stride elements -> rows of N values at out_stride elements */
+PDSP_API int pdsp_ntt_forward_u64(const pdsp_ntt *h, long long batch, const uint64_t *in, long long in_stride,
+                                  uint64_t *out, long long out_stride, pdsp_stream stream);
+PDSP_API int pdsp_ntt_inverse_u64(const pdsp_ntt *h, long long batch, const uint64_t *in, long long in_stride,
+                                  uint64_t *out, long long out_stride, pdsp_stream stream);
+PDSP_API int pdsp_ntt_conv_u64(const pdsp_ntt *h, long long batch, const uint64_t *a, long long a_len,
+                               long long a_stride, const uint64_t *b, long long b_len, long long b_stride,
+                               uint64_t *out, long long out_len, long long out_stride, pdsp_stream stream);
+/* out[i] = a[i] b[i] mod p, i < count; out may be a or b itself, no other overlap */
+PDSP_API int pdsp_ntt_mul_u64(long long count, const uint64_t *a, const uint64_t *b, uint64_t *out,
+                              pdsp_stream stream);
+/* synchronous host forms: `batch` contiguous rows of n values in and out */
+PDSP_API int pdsp_ntt_host_u64(const uint64_t *x, long long batch, long long n, int inverse, uint64_t *out);
+/* rows a [batch, a_len] and b ([batch, b_len], or one row when b_shared != 0) -> rows [batch, out_len] of the
+ * n-point convolution */
+PDSP_API int pdsp_ntt_conv_host_u64(const uint64_t *a, long long a_len, const uint64_t *b, long long b_len,
+                                    int b_shared, long long batch, long long n, uint64_t *out, long long out_len);
+/* device-free helpers on the arithmetic the kernels use: p; omega_n (0: n is no power of two <= 2^32); a b, a^e and
+ * a^-1 mod p for any 64-bit patterns (invmod of 0 mod p is 0) */
+PDSP_API uint64_t pdsp_ntt_modulus(void);
+PDSP_API uint64_t pdsp_ntt_root(long long n);
+PDSP_API uint64_t pdsp_ntt_mulmod(uint64_t a, uint64_t b);
+PDSP_API uint64_t pdsp_ntt_powmod(uint64_t a, uint64_t e);
+PDSP_API uint64_t pdsp_ntt_invmod(uint64_t a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -66,6 +66,7 @@ def _load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     ll, i32, dbl, vp = C.c_longlong, C.c_int, C.c_double, C.c_void_p
     dp = C.POINTER(C.c_double)
+    u64 = C.c_uint64
     sigs = {
         "pdsp_version": ([], i32),
         "pdsp_last_error": ([], C.c_char_p),
@@ -184,6 +185,20 @@ def _load() -> C.CDLL:
         "pdsp_dwt_inverse_f64": ([vp, ll, vp, ll, ll, vp, ll, vp], i32),
         "pdsp_dwt_forward_host_f64": ([dp, ll, ll, C.c_char_p, dp, ll, i32, dp], i32),
         "pdsp_dwt_inverse_host_f64": ([dp, ll, ll, C.c_char_p, dp, ll, i32, dp], i32),
+        "pdsp_ntt_create": ([ll, i32, C.POINTER(vp)], i32),
+        "pdsp_ntt_destroy": ([vp], i32),
+        "pdsp_ntt_size": ([vp], ll),
+        "pdsp_ntt_forward_u64": ([vp, ll, vp, ll, vp, ll, vp], i32),
+        "pdsp_ntt_inverse_u64": ([vp, ll, vp, ll, vp, ll, vp], i32),
+        "pdsp_ntt_conv_u64": ([vp, ll, vp, ll, ll, vp, ll, ll, vp, ll, ll, vp], i32),
+        "pdsp_ntt_mul_u64": ([ll, vp, vp, vp, vp], i32),
+        "pdsp_ntt_host_u64": ([vp, ll, ll, i32, vp], i32),
+        "pdsp_ntt_conv_host_u64": ([vp, ll, vp, ll, i32, ll, ll, vp, ll], i32),
+        "pdsp_ntt_modulus": ([], u64),
+        "pdsp_ntt_root": ([ll], u64),
+        "pdsp_ntt_mulmod": ([u64, u64], u64),
+        "pdsp_ntt_powmod": ([u64, u64], u64),
+        "pdsp_ntt_invmod": ([u64], u64),
         "pdsp_set_upfirdn_tile": ([i32], i32),
         "pdsp_set_dwt_tile": ([i32], i32),
         "pdsp_dev_dwt_tile": ([ll, i32, ll, i32, i32, C.POINTER(ll)], i32),

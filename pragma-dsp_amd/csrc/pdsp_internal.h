@@ -1,6 +1,6 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from twelve translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from thirteen translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
@@ -15,6 +15,7 @@
 //   pdsp_kernels_dft.hip          any-length DFT (Bluestein's chirp-z algorithm), f32 and f64
 //   pdsp_kernels_dwt.hip          multi-level wavelet transform (wavedec / waverec), f32 and f64
 //   pdsp_kernels_czt.hip          chirp-z transform and zoom FFT (czt / zoom_fft), f32 and f64
+//   pdsp_kernels_ntt.hip          number-theoretic transform and exact convolution over GF(2^64 - 2^32 + 1)
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -374,5 +375,18 @@ int czt_dev(int log2m, long long len, long long bins, long long batch, const T *
             long long in_stride, T *re_out, T *im_out, long long out_stride, const typename pdsp::vec2<T>::type *pre,
             const typename pdsp::vec2<T>::type *post, const typename pdsp::vec2<T>::type *bt,
             const typename pdsp::vec2<T>::type *tw, hipStream_t s);
+
+// pdsp_ntt_* after validation (pdsp_kernels_ntt.hip): kNttMinLog2N <= log2n <= kNttMaxLog2N, op a pdsp::NttOp (0 forward,
+// 1 inverse, 2 convolution), 1 <= batch with at most 2^31 - 1 workgroups, 1 <= a_len, b_len, out_len <= N (transforms:
+// a_len = out_len = N, b unused), strides >= the lengths (b_stride 0: one shared row); tw: omega_N^j, j < N / 2.  out == a
+// with equal strides is allowed (a thread stores the positions it loaded), no other overlap.
+constexpr int kNttMinLog2N = 6, kNttMaxLog2N = 14;
+int ntt_dev(int log2n, int op, long long batch, const uint64_t *a, long long a_stride, int a_len, const uint64_t *b,
+            long long b_stride, int b_len, uint64_t *out, long long out_stride, int out_len, const uint64_t *tw,
+            hipStream_t s);
+// workgroups of that launch (rows per workgroup: pdsp_ntt_kernel.h, NttTraits)
+long long ntt_blocks(int log2n, int op, long long batch);
+// out[i] = a[i] b[i] mod p, i < count, count >= 1
+int ntt_mul_dev(long long count, const uint64_t *a, const uint64_t *b, uint64_t *out, hipStream_t s);
 
 }  // namespace pdsp_host

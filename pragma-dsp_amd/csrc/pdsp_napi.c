@@ -824,6 +824,58 @@ static napi_value Dwt(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* BigUint64Array -> (uint64_t*, length).  null/undefined -> (NULL, 0). */
+static int u64_array(napi_env env, napi_value v, uint64_t **data, size_t *len) {
+  napi_valuetype t;
+  *data = NULL;
+  *len = 0;
+  if (napi_typeof(env, v, &t) != napi_ok) return 0;
+  if (t == napi_null || t == napi_undefined) return 1;
+  bool is_ta = false;
+  napi_typedarray_type tt;
+  void *p = NULL;
+  size_t n = 0;
+  if (napi_is_typedarray(env, v, &is_ta) != napi_ok || !is_ta ||
+      napi_get_typedarray_info(env, v, &tt, &n, &p, NULL, NULL) != napi_ok || tt != napi_biguint64_array) {
+    napi_throw_type_error(env, NULL, "pdsp_napi: expected a BigUint64Array");
+    return 0;
+  }
+  *data = (uint64_t *)p;
+  *len = n;
+  return 1;
+}
+
+/* ntt(mode, a, b, n, y): mode 0 = the transform, 1 = its inverse of one row of a.length = n points into y (b null);
+ * mode 2 = the first y.length values of the n-point cyclic product of the rows a and b.  The integers are read first
+ * and the typed-array pointers last, as in dct().  Sizes the library refuses reach it unchanged (it fails before
+ * touching y), so its message is what the caller sees. */
+static napi_value Ntt(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return NULL;
+  int64_t mode, n;
+  uint64_t *a, *b, *y;
+  size_t na, nb, ny;
+  if (!get_i64(env, argv[0], &mode) || !get_i64(env, argv[3], &n) || !u64_array(env, argv[1], &a, &na) ||
+      !u64_array(env, argv[2], &b, &nb) || !u64_array(env, argv[4], &y, &ny))
+    return NULL;
+  int rc;
+  if (mode == 2) {
+    rc = pdsp_ntt_conv_host_u64(a, (long long)na, b, (long long)nb, 1, 1, (long long)n, y, (long long)ny);
+  } else {
+    if ((int64_t)na != n) {
+      napi_throw_error(env, NULL, "pdsp_napi: ntt input length differs from the size");
+      return NULL;
+    }
+    if (n >= 64 && n <= 16384 && (int64_t)ny < n) {
+      napi_throw_error(env, NULL, "pdsp_napi: ntt output too small");
+      return NULL;
+    }
+    rc = pdsp_ntt_host_u64(a, 1, (long long)n, mode != 0, y);
+  }
+  if (rc != PDSP_OK) return throw_pdsp(env);
+  return NULL;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   const struct {
     const char *name;
@@ -838,7 +890,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"firFilter", FirFilter},   {"resamplePoly", ResamplePoly}, {"upfirdn", Upfirdn},
       {"resampleDesign", ResampleDesign},   {"stft", Stft},               {"istft", Istft},
       {"dct", Dct},                 {"hilbert", Hilbert},         {"dft", Dft},
-      {"dwt", Dwt},                 {"czt", Czt},
+      {"dwt", Dwt},                 {"czt", Czt},                 {"ntt", Ntt},
   };
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
     napi_value f;

@@ -9,6 +9,7 @@ import * as hilbertNs from './hilbert';
 import * as dftNs from './dft';
 import * as waveletNs from './wavelet';
 import * as cztNs from './czt';
+import * as nttNs from './ntt';
 
 export { spectrum, spectrumBatch, spectrumStream, SpectrumOptions, SpectrumPeak, SpectrumResult } from './spectrum';
 export { ComplexArray } from './core';
@@ -19,6 +20,7 @@ export { DctType, DctNorm, DctOptions } from './dct';
 export { HilbertOptions, AnalyticSignal } from './hilbert';
 export { DftResult } from './dft';
 export { CztInput, CztOptions, ZoomFftOptions, CztResult } from './czt';
+export { Words } from './ntt';
 
 export const core: {
   createComplexArray: typeof coreNs.createComplexArray;
@@ -67,4 +69,10 @@ export const wavelet: {
 export const czt: {
   czt: typeof cztNs.czt;
   zoomFft: typeof cztNs.zoomFft;
+};
+export const ntt: {
+  ntt: typeof nttNs.ntt;
+  intt: typeof nttNs.intt;
+  polymul: typeof nttNs.polymul;
+  MODULUS: typeof nttNs.MODULUS;
 };

@@ -10,6 +10,7 @@
 //   require('.../js').dft        -> the DFT of any length 2 ... 4096 (an extension: the reference has powers of two only)
 //   require('.../js').wavelet    -> the multi-level wavelet transform (ROADMAP.md, "E) Wavelets")
 //   require('.../js').czt        -> the chirp-z transform and zoom FFT (an extension: scipy.signal.czt / zoom_fft)
+//   require('.../js').ntt        -> the number-theoretic transform and exact products (ROADMAP.md, "F) NTT")
 const core = require('./core');
 const fourier = require('./fourier');
 const s = require('./spectrum');
@@ -21,6 +22,7 @@ const resample = require('./resample');
 const dft = require('./dft');
 const wavelet = require('./wavelet');
 const czt = require('./czt');
+const ntt = require('./ntt');
 
 module.exports = {
   spectrum: s.spectrum,
@@ -82,5 +84,10 @@ Object.defineProperty(module.exports, 'wavelet', {
 // Chirp-z transform and zoom FFT: an extension beside the any-length DFT, not enumerated for the same reason.
 Object.defineProperty(module.exports, 'czt', {
   value: { czt: czt.czt, zoomFft: czt.zoomFft },
+  enumerable: false,
+});
+// Number-theoretic transform: planned by the reference (ROADMAP.md, item F), not enumerated for the same reason.
+Object.defineProperty(module.exports, 'ntt', {
+  value: { ntt: ntt.ntt, intt: ntt.intt, polymul: ntt.polymul, MODULUS: ntt.MODULUS },
   enumerable: false,
 });
