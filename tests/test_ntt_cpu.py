@@ -74,6 +74,13 @@ def test_mulmod_on_corner_pairs_and_random_pairs(pdsp):
     for _ in range(10 ** 4):
         a, b = rng.getrandbits(64), rng.getrandbits(64)
         assert lib.pdsp_ntt_mulmod(a, b) == a * b % P, (a, b)
+    # pairs built to take reduce128's borrow and final canon (uniform pairs take either once in 2^32): the host build
+    # of the header on the pairs test_gpu_ntt_paths.py puts through ntt_mul_kernel
+    import ntt_model
+    pairs = ntt_model.targeted_pairs()
+    assert {branch for _, _, branch in pairs} == {"borrow", "canon"} and len(pairs) >= 300
+    for a, b, _ in pairs:
+        assert lib.pdsp_ntt_mulmod(a, b) == a * b % P, (a, b)
 
 
 def test_invmod_and_powmod(pdsp):
