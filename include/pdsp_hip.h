@@ -765,6 +765,74 @@ PDSP_API uint64_t pdsp_ntt_mulmod(uint64_t a, uint64_t b);
 PDSP_API uint64_t pdsp_ntt_powmod(uint64_t a, uint64_t e);
 PDSP_API uint64_t pdsp_ntt_invmod(uint64_t a);
 
+/* ---- sliding DFT: chosen bins of a window at every hop, f32 / f64 -------------------------------- */
+/* A row x has T real samples.  The handle holds a window length N, any integer in 2 <= N <= 16384 (not only powers of
+ * two), a hop h >= 1, K bins b_0 ... b_{K-1} -- finite f64 numbers of CYCLES PER WINDOW, fractional, negative and >= N
+ * all allowed -- and a window type, one of the four of pdsp_window_make.  For each bin j and frame m = 0 ... F - 1,
+ * F = 1 + floor((T - N) / h) (T < N is PDSP_ERR_INPUT_LENGTH):
+ *   Y[j][m] = sum_{n < N} w[n] x[m h + n] exp(-2 pi i b_j n / N)
+ * unscaled, the phase referenced to the frame's own first sample: Y[j][m] is numpy.fft.fft(w * x[m h : m h + N])[b_j]
+ * for an integer b_j, and for a power-of-two N in 64 ... 16384 and an integer b_j <= N / 2 the bin of pdsp_stft_complex
+ * with frame_len = N and the same window.
+ * Windows without a window pass.  The library's windows are symmetric cosine sums in 2 pi n / (N - 1), and with
+ * a = (1) for rect, (.5, .5) for Hann, (.54, .46) for Hamming and (.42, .5, .08) for Blackman
+ *   sum w x e^(-2 pi i b n / N) = a_0 X(b) + sum_{c >= 1} (-1)^c a_c / 2 [X(b + c N / (N - 1)) + X(b - c N / (N - 1))]
+ * with X the rectangular sum, so a windowed bin is 1, 3 or 5 COMPONENTS of the rectangular sliding sum at fractional
+ * bins, added in registers before the store (pdsp_sdft_components() reports the count, pdsp_sdft_window_weights() the
+ * weights in table order: 0, +1, -1, +2, -2).
+ * Phases are exact.  The table entry of component (b, +-c) at position i in [0, N] is exp(-2 pi i (t1 +- t2)):
+ *   t1 = ((b i) mod N) / N, b i an error-free product (p = b i, e = fma(b, i, -p)), p reduced with fmod, e added
+ *        after the reduction -- the rule of the CZT's tables above -- and N added where the sum is negative;
+ *   t2 = ((c i) mod (N - 1)) / (N - 1), in integers;
+ * cos and sin are evaluated in long double and rounded once per precision.  Integer bins get the exact N-th roots of
+ * unity, and b and b + N give the same table and the same output bits.  Note that a bin of 0.1 is the double NEAREST
+ * 0.1, not 1/10: it lies 5.6e-18 cycles above, which is 3.5e-17 rad at the window's end whatever N.  The tables follow
+ * the double (in long double the two differ in the 17th digit; rounded to f64 one entry in sixteen lands on the
+ * neighbouring value at N = 1000) -- far less than the CZT's step shows, because a bin is multiplied by n / N <= 1 and not by n k
+ * (pdsp_sdft_phase_table() gives the table of one component, device-free).
+ * The algorithm is parallel in time, O(K) per sample and has no drift: the row is cut into anchored chunks of N
+ * samples, every frame is the suffix of one chunk's products x tab plus tab[N] times the prefix of the next chunk's,
+ * and both come from scans of their own (pdsp_sdft_kernel.h states the one summation order).  A frame's value is a
+ * function of its own N samples and of (m h) mod N alone: the bits do not depend on the batch, the strides, T, the
+ * hop, the tiling or the other bins of the handle, a NaN or Inf reaches exactly the frames that contain it, and frame
+ * 10^6 has the error of frame 0.  Error: a few u sqrt(N) max|x| in the worst case over a call, u the unit roundoff
+ * (DESIGN.md 4.15 has the measured figures).
+ * Limits: 1 <= K <= 256 and K components (N + 1) <= 2^21 table entries, N outside 2 ... 16384:
+ * PDSP_ERR_UNSUPPORTED_SIZE; hop < 1, an unknown window, a null, non-finite or |b| >= 2^53 bin: PDSP_ERR_BAD_ARG.
+ * Argument errors of pdsp_sdft_create are reported before any device work (device = -1 gets them on a machine without
+ * a GPU) and leave *out untouched.  The tables belong to the object and go to `device` (< 0: the current one) when it
+ * is created.
+ * Launches: series (r, j) of row r and bin j starts at (r K + j) out_stride in each plane, out_stride >= F; only the F
+ * values of a series are written, and nothing outside [0, T) of a row is read.  A null handle or buffer, batch < 1,
+ * in_stride < T, out_stride < F, extents that overflow 64 bits, a grid of 2^31 workgroups, and any meeting of an
+ * output plane's byte extent with the input's or the other output plane's (there is no in-place form) give
+ * PDSP_ERR_BAD_ARG, before any device work. */
+typedef struct pdsp_sdft pdsp_sdft;
+PDSP_API int pdsp_sdft_create(long long window_len, long long nbins, const double *bins, long long hop,
+                              int window_type, int device, pdsp_sdft **out);
+PDSP_API int pdsp_sdft_destroy(pdsp_sdft *c);
+PDSP_API long long pdsp_sdft_length(const pdsp_sdft *c);
+PDSP_API long long pdsp_sdft_bins(const pdsp_sdft *c);
+PDSP_API double pdsp_sdft_bin(const pdsp_sdft *c, long long index);
+PDSP_API long long pdsp_sdft_hop(const pdsp_sdft *c);
+PDSP_API long long pdsp_sdft_components(const pdsp_sdft *c);
+/* F for rows of `samples` values; 0 where samples < N */
+PDSP_API long long pdsp_sdft_frames(const pdsp_sdft *c, long long samples);
+/* `batch` rows of `samples` values at in_stride -> per row and bin a series of F values in each plane */
+PDSP_API int pdsp_sdft_f32(const pdsp_sdft *c, long long batch, const float *in, long long in_stride,
+                           long long samples, float *re_out, float *im_out, long long out_stride, pdsp_stream stream);
+PDSP_API int pdsp_sdft_f64(const pdsp_sdft *c, long long batch, const double *in, long long in_stride,
+                           long long samples, double *re_out, double *im_out, long long out_stride,
+                           pdsp_stream stream);
+/* synchronous f64 host form: `batch` contiguous rows of `samples` values in, contiguous planes [batch][nbins][F] out */
+PDSP_API int pdsp_sdft_host_f64(const double *in, long long batch, long long samples, long long window_len,
+                                long long nbins, const double *bins, long long hop, int window_type, double *re_out,
+                                double *im_out);
+/* device-free: the component weights of a window in table order (returns their number, 0 for an unknown type), and
+ * the window_len + 1 table entries of component c in -2 ... 2 of one bin */
+PDSP_API int pdsp_sdft_window_weights(int window_type, double weights[5]);
+PDSP_API int pdsp_sdft_phase_table(long long window_len, double bin, int component, double *re_out, double *im_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@ from .resample import (  # noqa: F401
 )
 from .wavelet import Dwt, wavedec, wavedecHost, wavelet_taps, waverec, waverecHost  # noqa: F401
 from .ntt import NTT_MODULUS, Ntt, convolve_exact, intt, ntt, ntt_mul, ntt_root, polymul  # noqa: F401
+from .sdft import SlidingDft, goertzel, sliding_dft  # noqa: F401
 
 __all__ = [
     "ComplexArray", "Radix2Fft", "createComplexArray", "isPowerOfTwo", "nextPowerOfTwo",
@@ -47,4 +48,5 @@ __all__ = [
     "Resampler", "Upfirdn", "resample_poly", "upfirdn", "resamplePoly", "upfirdnHost", "design_taps",
     "Dwt", "wavedec", "waverec", "wavedecHost", "waverecHost", "wavelet_taps",
     "Ntt", "ntt_mul", "ntt", "intt", "polymul", "convolve_exact", "NTT_MODULUS", "ntt_root",
+    "SlidingDft", "sliding_dft", "goertzel",
 ]

@@ -199,6 +199,19 @@ def _load() -> C.CDLL:
         "pdsp_ntt_mulmod": ([u64, u64], u64),
         "pdsp_ntt_powmod": ([u64, u64], u64),
         "pdsp_ntt_invmod": ([u64], u64),
+        "pdsp_sdft_create": ([ll, ll, dp, ll, i32, i32, C.POINTER(vp)], i32),
+        "pdsp_sdft_destroy": ([vp], i32),
+        "pdsp_sdft_length": ([vp], ll),
+        "pdsp_sdft_bins": ([vp], ll),
+        "pdsp_sdft_bin": ([vp, ll], dbl),
+        "pdsp_sdft_hop": ([vp], ll),
+        "pdsp_sdft_components": ([vp], ll),
+        "pdsp_sdft_frames": ([vp, ll], ll),
+        "pdsp_sdft_f32": ([vp, ll, vp, ll, ll, vp, vp, ll, vp], i32),
+        "pdsp_sdft_f64": ([vp, ll, vp, ll, ll, vp, vp, ll, vp], i32),
+        "pdsp_sdft_host_f64": ([dp, ll, ll, ll, ll, dp, ll, i32, dp, dp], i32),
+        "pdsp_sdft_window_weights": ([i32, dp], i32),
+        "pdsp_sdft_phase_table": ([ll, dbl, i32, dp, dp], i32),
         "pdsp_set_upfirdn_tile": ([i32], i32),
         "pdsp_set_dwt_tile": ([i32], i32),
         "pdsp_dev_dwt_tile": ([ll, i32, ll, i32, i32, C.POINTER(ll)], i32),

@@ -1,6 +1,6 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from thirteen translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from fourteen translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
@@ -16,6 +16,7 @@
 //   pdsp_kernels_dwt.hip          multi-level wavelet transform (wavedec / waverec), f32 and f64
 //   pdsp_kernels_czt.hip          chirp-z transform and zoom FFT (czt / zoom_fft), f32 and f64
 //   pdsp_kernels_ntt.hip          number-theoretic transform and exact convolution over GF(2^64 - 2^32 + 1)
+//   pdsp_kernels_sdft.hip         sliding DFT (chosen bins at every hop), f32 and f64
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -388,5 +389,19 @@ int ntt_dev(int log2n, int op, long long batch, const uint64_t *a, long long a_s
 long long ntt_blocks(int log2n, int op, long long batch);
 // out[i] = a[i] b[i] mod p, i < count, count >= 1
 int ntt_mul_dev(long long count, const uint64_t *a, const uint64_t *b, uint64_t *out, hipStream_t s);
+
+// pdsp_sdft_* after validation (pdsp_kernels_sdft.hip): 2 <= n <= 16384, hop >= 1, 1 <= nbins <= 256, ncomp 1, 3 or 5
+// with their weights, samples >= n, in_stride >= samples, out_stride >= 1 + (samples - n) / hop, batch >= 1 with
+// sdft_blocks() < 2^31, no overlap; tab: per bin and component n + 1 phases (pdsp_sdft_kernel.h).
+// E, the positions per thread: the summation order depends on n and the precision through it alone (f64 keeps 4: at 8
+// its kernel runs out of scalar registers)
+inline int sdft_segment(long long n, size_t elem) { return elem == 4 && n > 1024 ? 8 : 4; }
+int sdft_tile_chunks(long long n, size_t elem);
+// workgroups of that launch, or -1 where the product overflows
+long long sdft_blocks(long long n, size_t elem, long long samples, long long nbins, long long batch);
+template <typename T>
+int sdft_dev(long long n, long long hop, int nbins, int ncomp, const double *weights, long long batch, const T *in,
+             long long in_stride, long long samples, T *re_out, T *im_out, long long out_stride,
+             const typename pdsp::vec2<T>::type *tab, hipStream_t s);
 
 }  // namespace pdsp_host

@@ -649,6 +649,33 @@ static napi_value Stft(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* sdft(signal, size, bins, hop, windowType, real, imag): real / imag receive bins.length series of F values,
+ * F = 1 + (len - size) / hop, of the sliding DFT of one signal (include/pdsp_hip.h, "sliding DFT").  The integers are
+ * read first and the typed-array pointers last; arguments the library refuses reach it unchanged (it fails before
+ * touching the outputs), so its message is what the caller sees. */
+static napi_value Sdft(napi_env env, napi_callback_info info) {
+  napi_value argv[7];
+  if (!get_args(env, info, 7, argv)) return NULL;
+  double *x, *bins, *re, *im;
+  size_t nx, nb, nre, nim;
+  int64_t n, hop, win;
+  if (!get_i64(env, argv[1], &n) || !get_i64(env, argv[3], &hop) || !get_i64(env, argv[4], &win) ||
+      !f64_array(env, argv[0], &x, &nx) || !f64_array(env, argv[2], &bins, &nb) || !f64_array(env, argv[5], &re, &nre) ||
+      !f64_array(env, argv[6], &im, &nim))
+    return NULL;
+  if (n >= 2 && n <= 16384 && hop >= 1 && (int64_t)nx >= n && nb >= 1 && nb <= 256) {
+    const int64_t frames = 1 + ((int64_t)nx - n) / hop, need = frames * (int64_t)nb;  /* nx < 2^53, nb <= 256 */
+    if ((int64_t)nre < need || (int64_t)nim < need) {
+      napi_throw_error(env, NULL, "pdsp_napi: sdft output too small");
+      return NULL;
+    }
+  }
+  if (pdsp_sdft_host_f64(x, 1, (long long)nx, (long long)n, (long long)nb, bins, (long long)hop, (int)win, re, im) !=
+      PDSP_OK)
+    return throw_pdsp(env);
+  return NULL;
+}
+
 /* istft(real, imag, frames, fftSize, hopSize, windowType, out): out receives (frames - 1) hopSize + fftSize samples. */
 static napi_value Istft(napi_env env, napi_callback_info info) {
   napi_value argv[7];
@@ -891,6 +918,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"resampleDesign", ResampleDesign},   {"stft", Stft},               {"istft", Istft},
       {"dct", Dct},                 {"hilbert", Hilbert},         {"dft", Dft},
       {"dwt", Dwt},                 {"czt", Czt},                 {"ntt", Ntt},
+      {"sdft", Sdft},
   };
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
     napi_value f;

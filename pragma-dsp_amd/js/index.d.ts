@@ -10,6 +10,7 @@ import * as dftNs from './dft';
 import * as waveletNs from './wavelet';
 import * as cztNs from './czt';
 import * as nttNs from './ntt';
+import * as sdftNs from './sdft';
 
 export { spectrum, spectrumBatch, spectrumStream, SpectrumOptions, SpectrumPeak, SpectrumResult } from './spectrum';
 export { ComplexArray } from './core';
@@ -21,6 +22,7 @@ export { HilbertOptions, AnalyticSignal } from './hilbert';
 export { DftResult } from './dft';
 export { CztInput, CztOptions, ZoomFftOptions, CztResult } from './czt';
 export { Words } from './ntt';
+export { SdftWindow, SlidingDftResult, GoertzelResult } from './sdft';
 
 export const core: {
   createComplexArray: typeof coreNs.createComplexArray;
@@ -75,4 +77,8 @@ export const ntt: {
   intt: typeof nttNs.intt;
   polymul: typeof nttNs.polymul;
   MODULUS: typeof nttNs.MODULUS;
+};
+export const sdft: {
+  slidingDft: typeof sdftNs.slidingDft;
+  goertzel: typeof sdftNs.goertzel;
 };

@@ -11,6 +11,7 @@
 //   require('.../js').wavelet    -> the multi-level wavelet transform (ROADMAP.md, "E) Wavelets")
 //   require('.../js').czt        -> the chirp-z transform and zoom FFT (an extension: scipy.signal.czt / zoom_fft)
 //   require('.../js').ntt        -> the number-theoretic transform and exact products (ROADMAP.md, "F) NTT")
+//   require('.../js').sdft       -> the sliding DFT: chosen bins at every hop (ROADMAP.md, "B) Sliding DFT")
 const core = require('./core');
 const fourier = require('./fourier');
 const s = require('./spectrum');
@@ -23,6 +24,7 @@ const dft = require('./dft');
 const wavelet = require('./wavelet');
 const czt = require('./czt');
 const ntt = require('./ntt');
+const sdft = require('./sdft');
 
 module.exports = {
   spectrum: s.spectrum,
@@ -89,5 +91,10 @@ Object.defineProperty(module.exports, 'czt', {
 // Number-theoretic transform: planned by the reference (ROADMAP.md, item F), not enumerated for the same reason.
 Object.defineProperty(module.exports, 'ntt', {
   value: { ntt: ntt.ntt, intt: ntt.intt, polymul: ntt.polymul, MODULUS: ntt.MODULUS },
+  enumerable: false,
+});
+// Sliding DFT: planned by the reference (ROADMAP.md, item B), not enumerated for the same reason.
+Object.defineProperty(module.exports, 'sdft', {
+  value: { slidingDft: sdft.slidingDft, goertzel: sdft.goertzel },
   enumerable: false,
 });
