@@ -33,10 +33,15 @@ int sdft_dev(long long n, long long hop, int nbins, int ncomp, const double *wei
   const long long blocks = ntiles * nbins * batch;
   pdsp::SdftWeights<T> w{};
   for (int i = 0; i < ncomp; ++i) w.w[i] = (T)weights[i];
+  // The kernel's hop is min(hop, T - N + 1).  The starts are the multiples of hop up to T - N: a hop beyond T - N
+  // leaves start 0 alone, as T - N + 1 does, and any smaller hop is passed as it is.  The kernel rounds a chunk's base
+  // up to a multiple of its hop in 64 bits; with hop <= T - N + 1 that sum stays below 2 T (the caller's hop has no
+  // upper limit, and cbase + hop overflowed from 2^63 - cbase on).  Frame counts and pdsp_sdft_hop keep the caller's.
+  const long long khop = hop < samples - n + 1 ? hop : samples - n + 1;
   const auto go = [&](auto e) {
     constexpr int E = decltype(e)::value;
     hipLaunchKernelGGL((pdsp::sdft_kernel<T, E>), dim3((unsigned)blocks), dim3(pdsp::kSdftWG), 0, s, in, in_stride,
-                       samples, (int)n, hop, re_out, im_out, out_stride, reinterpret_cast<const pdsp::cx<T> *>(tab),
+                       samples, (int)n, khop, re_out, im_out, out_stride, reinterpret_cast<const pdsp::cx<T> *>(tab),
                        nbins, ncomp, w, (int)tc, (unsigned)ntiles, nchunks);
     return hipGetLastError();
   };

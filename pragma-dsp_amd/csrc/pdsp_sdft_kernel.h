@@ -158,6 +158,8 @@ __device__ __forceinline__ cx<T> sdft_sum_down(const cx<T> *v, const int first, 
 
 // in: `batch` rows of `samples` values at in_stride; re_out / im_out: series (row, bin) of `frames` values at
 // (row nbins + bin) out_stride.  tab: per bin and component n + 1 entries.  Grid: bins fastest, then tiles, then rows.
+// hop: 1 <= hop <= samples - n + 1.  The host passes min(caller's hop, samples - n + 1), which names the same starts
+// (a hop beyond samples - n leaves start 0 alone); cbase + hop - 1 below is then under 2 samples and cannot overflow.
 template <typename T, int E>
 __global__ void __launch_bounds__(kSdftWG)
 sdft_kernel(const T *__restrict__ in, const long long in_stride, const long long samples, const int n,

@@ -4,12 +4,13 @@ the library.
     direct()   long double direct sums  Y[j][m] = sum_n w[n] x[m h + n] exp(-2 pi i b_j n / N)  with the exact phase
                rule and the window's cosine sum evaluated in long double -- of all frames, or of the frames asked for
     emulate()  the kernel's documented summation order (pdsp_sdft_kernel.h) in numpy, in f32 or f64, or with plain
-               sequential scans of a chunk (order="sequential") as the yardstick the device's bound must stay below
+               sequential scans of a chunk (order="sequential") as the yardstick the device's bound must stay below;
+               with exact=True every fma is rounded once (fma32 / fma64): the device's bits, frame for frame
     sliding()  every frame of a rectangular bin from ONE long double prefix sum over the row: the full-coverage check
                (its own error is 2^-64 sqrt(T)-ish, three orders below f64's)
 
-and the shapes the CPU and GPU tests share (SIZES, lengths, hops, bins_of, windows_of), their inputs and the error
-metric.  Reference values are cached per
+and the shapes the CPU and GPU tests share (SIZES, lengths, hops, bins_of, windows_of; PATH_SIZES and the path_*
+functions of the path-by-path tests), their inputs and the error metric.  Reference values are cached per
 case: the CPU test and the GPU tests of one session compute each once.
 """
 import functools
@@ -114,16 +115,63 @@ def sliding(x, n, b, hop=1):
 
 # ---- the kernel's order in numpy ------------------------------------------------------------------------------------
 
+def _two_sum(a, b):
+    """(s, e) with s = fl(a + b) and s + e = a + b exactly (Knuth; f64, no overflow)."""
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _to_odd(s, e):
+    """fl(a + b) rounded to odd, from TwoSum's (s, e): where the sum is inexact and s's last bit is even, the
+    neighbour of s on e's side (it is odd, and the exact sum lies between the two)."""
+    fix = (e != 0) & ((s.view(np.int64) & 1) == 0)
+    return np.where(fix, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+
+
+def _split(a):
+    """Veltkamp: a = hi + lo, each of at most 26 significant bits."""
+    c = 134217729.0 * a  # 2^27 + 1
+    hi = c - (c - a)
+    return hi, a - hi
+
+
+def fma32(a, b, c):
+    """fmaf(a, b, c) of f32 arrays, correctly rounded: the product is exact in f64 (48 bits), the sum is rounded to
+    odd in f64 (53 >= 2 x 24 + 2 bits: the second rounding then sees what one rounding of the exact value sees)."""
+    a, b, c = (np.asarray(v, dtype=np.float32).astype(np.float64) for v in (a, b, c))
+    a, b, c = np.broadcast_arrays(a, b, c)
+    return _to_odd(*_two_sum(a * b, c)).astype(np.float32)
+
+
+def fma64(a, b, c):
+    """fma(a, b, c) of f64 arrays, correctly rounded (Boldo and Melquiond, "Emulation of a FMA and correctly rounded
+    sums: proved algorithms using rounding to odd", 2008): a b = uh + ul exactly (Dekker's product on Veltkamp's
+    split), c + uh = th + tl exactly, v = tl + ul rounded to odd, the result fl(th + v).  No overflow and no underflow
+    in the domain: signals of O(1), tables whose nonzero entries are normal."""
+    a, b, c = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (a, b, c)))
+    uh = a * b
+    ah, al = _split(a)
+    bh, bl = _split(b)
+    ul = al * bl - (((uh - ah * bh) - al * bh) - ah * bl)
+    th, tl = _two_sum(c, uh)
+    return th + _to_odd(*_two_sum(tl, ul))
+
+
 class _Arith:
     """Arithmetic of one precision with the kernel's fused operations.  f32: products are exact in f64, so
     fma(a, b, c) = f32(f64(a) f64(b) + f64(c)) (a double rounding, one case in 2^29).  f64: numpy has no fma; a product
-    and a sum stand in (two roundings where the device has one: the emulation's error is an upper estimate)."""
+    and a sum stand in (two roundings where the device has one: the emulation's error is an upper estimate).
+    exact: fma32 / fma64 above, one rounding as on the device -- the form the device is held to bit for bit."""
 
-    def __init__(self, dtype):
+    def __init__(self, dtype, exact=False):
         self.t = DT[dtype]
         self.f32 = dtype == "f32"
+        self.exact = exact
 
     def fma(self, a, b, c):
+        if self.exact:
+            return fma32(a, b, c) if self.f32 else fma64(a, b, c)
         if self.f32:
             return (a.astype(np.float64) * np.asarray(b, np.float64) + c.astype(np.float64)).astype(np.float32)
         return a * b + c
@@ -210,10 +258,10 @@ def _chunk_scans(ar, xs, tr, ti, e_seg, order):
     return res
 
 
-def emulate(x, n, bins, hop=1, win="rect", dtype="f32", order="device"):
+def emulate(x, n, bins, hop=1, win="rect", dtype="f32", order="device", exact=False):
     """complex [rows, K, F] in the precision's complex type: the kernel's arithmetic on the tables rounded once from
-    long double."""
-    ar = _Arith(dtype)
+    long double.  exact: every fma with one rounding (fma32 / fma64), the device's bits."""
+    ar = _Arith(dtype, exact)
     t = ar.t
     x = np.atleast_2d(np.asarray(x)).astype(t)
     rows, samples = x.shape
@@ -247,7 +295,7 @@ def emulate(x, n, bins, hop=1, win="rect", dtype="f32", order="device"):
                 acc_r, acc_i = w * yr, w * yi
             else:
                 acc_r, acc_i = ar.fma(yr, w, acc_r), ar.fma(yi, w, acc_i)
-        out[:, j, :] = acc_r + 1j * acc_i
+        out.real[:, j, :], out.imag[:, j, :] = acc_r, acc_i  # (part by part: a sum with 1j * im loses a zero's sign)
     return out
 
 
@@ -321,3 +369,44 @@ def err_units(got, re, im, n, dtype, xmax):
     """max |got - direct| / (u sqrt(N) max|x|): the metric of the bound (the windows' weights sum to 1 in magnitude)."""
     d = np.hypot(np.real(got).astype(LD) - re, np.imag(got).astype(LD) - im)
     return float(d.max() / (LD(U[dtype]) * np.sqrt(LD(n)) * LD(xmax)))
+
+
+# ---- the path-by-path cases (test_sdft_exact_cpu.py, test_gpu_sdft_paths.py) ----------------------------------------
+
+# N < E (2, 3, 5), the one-wave boundary (255 ... 257), f32's switch from E = 4 to E = 8 (1024 / 1025), the first second
+# round (f64 1025, f32 2049: one live position in the last round), N not a multiple of E over several rounds (4097,
+# 16383), f64's sixteenth round with one position (15361 = 15 x 1024 + 1) and the largest window.
+PATH_SIZES = (2, 3, 5, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 4097, 15361, 16383, 16384)
+PATH_WINDOWED = (3, 1025, 2049, 16384)
+PATH_ROWS = 2
+
+
+def path_lengths(n):
+    return lengths(n) if n <= 2049 else (n, 2 * n + 1, 3 * n + 7)
+
+
+def path_bins(n):
+    return (0.0, 12.5, -3.0, n / 2)
+
+
+def path_windows(n):
+    return ("rect", "hann", "blackman") if n in PATH_WINDOWED else ("rect",)
+
+
+def path_shape(n, win):
+    """(rows, bins) of a case of the CPU test, which also computes long double references: two rows of four bins; one
+    row of three where the emulation is slowest.  (The GPU test runs PATH_ROWS rows of path_bins everywhere.)"""
+    if n == 16384 and win != "rect":
+        return 1, path_bins(n)[:3]
+    return PATH_ROWS, path_bins(n)
+
+
+def rounds_of(n, dtype):
+    """Rounds of 256 E positions per chunk."""
+    return -(-n // (WG * segment(n, dtype)))
+
+
+@functools.lru_cache(maxsize=8)
+def emulated(n, t, win, dtype, rows, bins, seed=0):
+    """emulate(exact=True) at hop 1 on the first `rows` rows of signal(n, t, seed): the device's bits, frame by frame."""
+    return emulate(signal(n, t, seed)[:rows], n, bins, 1, win, dtype, exact=True)
