@@ -500,10 +500,11 @@ PDSP_API int pdsp_dct_host_f64(const double *x, long long batch, long long n, in
  * A row holds `len` samples, 1 <= len <= N, and is zero-padded to N (scipy.signal.hilbert(x, N=n)); every output row
  * has N samples.  out_mode selects what one launch writes per row:
  *   ANALYTIC  x[n], Hx[n] interleaved, 2N values (the real parts are the loaded samples bit for bit)
- *   IMAG      Hx[n]     ENVELOPE  sqrt(x[n]^2 + Hx[n]^2)     PHASE  atan2(Hx[n], x[n])        N values each
- * The envelope is formed as written, without scaling: it overflows where x^2 + Hx^2 does (|a| above ~1.8e19 in f32,
- * ~1.3e154 in f64) and loses its precision, then flushes to zero, where the squares are subnormal (|a| below ~1e-19
- * in f32, ~1.5e-154 in f64), unlike abs(scipy.signal.hilbert(x)), which is a hypot.
+ *   IMAG      Hx[n]     ENVELOPE  |x[n] + i Hx[n]|           PHASE  atan2(Hx[n], x[n])        N values each
+ * The f64 envelope is range-safe like abs(scipy.signal.hilbert(x)), a hypot: both parts are scaled by a power of two
+ * before they are squared, over the whole range of f64 (so are the host form and everything built on it).  The f32
+ * envelope squares in f32 (no hypot), as the f32 magnitude does: it holds its bound for samples with
+ * 1.1e-19 <= |a| <= 1.8e19; above, x^2 + Hx^2 overflows, below, the squares are subnormal and then zero.
  * N = pdsp_plan_size(), 64 <= N <= 16384 in both precisions (any other power of two: PDSP_ERR_UNSUPPORTED_SIZE).
  * f32 ~1e-7 * log2 N of max|a|, f64 ~1.6e-16 * log2 N.
  * Every argument is checked before any device work: a null plan or buffer, batch < 1, len outside 1 ... N,
