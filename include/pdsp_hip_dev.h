@@ -150,6 +150,22 @@ PDSP_API int pdsp_dev_host_transform_chunks(const pdsp_plan *plan, long long bat
 PDSP_API int pdsp_dev_host_spectrum_chunks(const pdsp_plan *plan, long long batch, int sides, int precision,
                                            long long info[2]);
 
+/* What the library holds at this moment, counted exactly (std::atomic counters touched where a resource is created or
+ * freed and nowhere on a launch path): the tests of re-entrancy, of the plan cache and of handle lifetimes compare
+ * them before and after.  info, PDSP_DEV_LIVE_INFO values:
+ *   [0] plans in the host forms' cache (at most 16 unless every entry is in use); [1] of those, entries a call is
+ *       running on right now (pinned: never evicted, kept by pdsp_plan_cache_clear)
+ *   [2] cached plans evicted to make room for another size since the library was loaded (pdsp_plan_cache_clear's
+ *       frees are not evictions)
+ *   [3] device tables alive -- every allocation a plan, a resampler, a dft, a czt, a dwt, an ntt or an sdft handle
+ *       uploaded and has not yet freed -- and [4] their bytes
+ *   [5] pinned host staging buffers and [6] device staging buffers of plans (the host-f64 transform and spectrum forms)
+ *   [7] streams the library created (a plan's own, and its slot streams of chunked host calls)
+ * The cache entries are read under the cache's lock; the rest are single atomic loads, so with calls in flight the
+ * values are each exact but not one snapshot.  Launches nothing, allocates nothing, needs no device. */
+#define PDSP_DEV_LIVE_INFO 8
+PDSP_API int pdsp_dev_live_resources(long long info[PDSP_DEV_LIVE_INFO]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,7 @@ def _load() -> C.CDLL:
         "pdsp_dev_spectrum_path_f64": ([vp, ll, vp, ll, ll, vp, i32, vp, vp, vp, vp, C.c_double, C.POINTER(i32)], i32),
         "pdsp_dev_host_transform_chunks": ([vp, ll, i32, C.POINTER(ll)], i32),
         "pdsp_dev_host_spectrum_chunks": ([vp, ll, i32, i32, C.POINTER(ll)], i32),
+        "pdsp_dev_live_resources": ([C.POINTER(ll)], i32),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -238,6 +239,16 @@ lib = _load()
 def check(rc: int) -> None:
     if rc != OK:
         raise PdspError(rc, lib.pdsp_last_error().decode("utf-8", "replace"))
+
+
+LIVE_FIELDS = ("cached_plans", "pinned", "evictions", "tables", "table_bytes", "host_stage", "dev_stage", "streams")
+
+
+def live_resources() -> dict:
+    """pdsp_dev_live_resources (include/pdsp_hip_dev.h) by field name: exact counters, for the tests."""
+    info = (C.c_longlong * len(LIVE_FIELDS))()
+    check(lib.pdsp_dev_live_resources(info))
+    return dict(zip(LIVE_FIELDS, info))
 
 
 def dptr(a):

@@ -74,6 +74,7 @@ hipMemPool_t scratch_pool() {
   return g_scratch_pool[dev];
 }
 std::atomic<unsigned long long> g_scratch_drawn{0};
+LiveCounters g_live;
 
 void trim_scratch_pools() {
   std::lock_guard<std::mutex> lk(g_scratch_pool_mu);
@@ -113,24 +114,42 @@ std::vector<T2> build_twiddles(int log2n, int log2e = 4) {
 
 // The plan's own stream, created on first use.  Caller holds plan->mu.
 int ensure_plan_stream(pdsp_plan *plan) {
-  if (!plan->stream) PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
+  if (!plan->stream) {
+    PDSP_HIP_TRY(hipStreamCreateWithFlags(&plan->stream, hipStreamNonBlocking));
+    ++g_live.streams;
+  }
   return PDSP_OK;
+}
+
+// The plan's staging buffers go back (g_live counts the buffers, not their bytes).  Caller holds plan->mu, or is the
+// last user of the plan.
+void free_host_stage(pdsp_plan *plan) {
+  if (!plan->h_stage) return;
+  (void)hipHostFree(plan->h_stage);
+  --g_live.host_stage;
+  plan->h_stage = nullptr;
+  plan->h_bytes = 0;
+}
+void free_dev_stage(pdsp_plan *plan) {
+  if (!plan->d_stage) return;
+  (void)hipFree(plan->d_stage);
+  --g_live.dev_stage;
+  plan->d_stage = nullptr;
+  plan->d_bytes = 0;
 }
 
 int ensure_stage(pdsp_plan *plan, size_t bytes) {
   if (int rc = ensure_plan_stream(plan)) return rc;
   if (plan->h_bytes < bytes) {
-    if (plan->h_stage) (void)hipHostFree(plan->h_stage);
-    plan->h_stage = nullptr;
-    plan->h_bytes = 0;
+    free_host_stage(plan);
     PDSP_HIP_TRY(hipHostMalloc(&plan->h_stage, bytes, hipHostMallocDefault));
+    ++g_live.host_stage;
     plan->h_bytes = bytes;
   }
   if (plan->d_bytes < bytes) {
-    if (plan->d_stage) (void)hipFree(plan->d_stage);
-    plan->d_stage = nullptr;
-    plan->d_bytes = 0;
+    free_dev_stage(plan);
     PDSP_HIP_TRY(hipMalloc(&plan->d_stage, bytes));
+    ++g_live.dev_stage;
     plan->d_bytes = bytes;
   }
   return PDSP_OK;
@@ -231,6 +250,7 @@ int cached_plan(long long n, CachedPlan *out) {
       if (victim == c.plans.end()) break;  // every entry is in use: grow past the bound rather than block
       pdsp_plan_destroy(victim->second.plan);
       c.plans.erase(victim);
+      ++g_live.evictions;
     }
     pdsp_plan *p = nullptr;
     if (int rc = pdsp_plan_create(n, dev, &p)) return rc;
@@ -248,16 +268,8 @@ int cached_plan(long long n, CachedPlan *out) {
 // repeat calls of ordinary sizes still cost no allocation.  Caller holds plan->mu.
 constexpr size_t kStageKeepBytes = (size_t)64 << 20;
 void trim_stage(pdsp_plan *plan) {
-  if (plan->h_bytes > kStageKeepBytes) {
-    (void)hipHostFree(plan->h_stage);
-    plan->h_stage = nullptr;
-    plan->h_bytes = 0;
-  }
-  if (plan->d_bytes > kStageKeepBytes) {
-    (void)hipFree(plan->d_stage);
-    plan->d_stage = nullptr;
-    plan->d_bytes = 0;
-  }
+  if (plan->h_bytes > kStageKeepBytes) free_host_stage(plan);
+  if (plan->d_bytes > kStageKeepBytes) free_dev_stage(plan);
 }
 
 // The one place a plan table reaches the device: allocate, copy, record the allocation with its owner
@@ -272,6 +284,9 @@ hipError_t upload_table(Tables<T> &t, const std::vector<E> &host, D **out) {
     return e;
   }
   t.owned.push_back(d);
+  t.owned_bytes += host.size() * sizeof(E);
+  ++g_live.tables;
+  g_live.table_bytes += (long long)(host.size() * sizeof(E));
   *out = (D *)d;
   return hipSuccess;
 }
@@ -588,6 +603,7 @@ int run_chunked(pdsp_plan *plan, long long rows, long long rows_per_chunk, int w
   while ((long long)plan->slot_streams.size() < (long long)kSlotsPerWorker * workers) {
     hipStream_t st = nullptr;
     PDSP_HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    ++g_live.streams;
     plan->slot_streams.push_back(st);
   }
   std::atomic<long long> next{0};
@@ -1148,6 +1164,22 @@ int pdsp_plan_cache_clear(void) {
   return PDSP_OK;
 }
 
+int pdsp_dev_live_resources(long long info[PDSP_DEV_LIVE_INFO]) {
+  if (!info) return fail(PDSP_ERR_BAD_ARG, "null buffer");
+  long long cached = 0, pinned = 0;
+  {
+    PlanCache &c = plan_cache();
+    std::lock_guard<std::mutex> lk(c.mu);
+    cached = (long long)c.plans.size();
+    for (const auto &kv : c.plans) pinned += kv.second.pins > 0;
+  }
+  const long long v[PDSP_DEV_LIVE_INFO] = {cached, pinned, g_live.evictions.load(), g_live.tables.load(),
+                                           g_live.table_bytes.load(), g_live.host_stage.load(), g_live.dev_stage.load(),
+                                           g_live.streams.load()};
+  std::memcpy(info, v, sizeof(v));
+  return PDSP_OK;
+}
+
 int pdsp_plan_destroy(pdsp_plan *plan) {
   if (!plan) return PDSP_OK;
   {
@@ -1155,17 +1187,19 @@ int pdsp_plan_destroy(pdsp_plan *plan) {
     if (plan->stream) {
       (void)hipStreamSynchronize(plan->stream);
       (void)hipStreamDestroy(plan->stream);
+      --g_live.streams;
     }
     for (hipStream_t st : plan->slot_streams) {
       (void)hipStreamSynchronize(st);
       (void)hipStreamDestroy(st);
+      --g_live.streams;
     }
     // a plan of a multi-pass size that drew scratch planes: the freed planes go back to the device with it
     const bool multipass = plan->t32.log2n1 > 0 || plan->t64.log2n1 > 0;
     plan->t32.release();
     plan->t64.release();
-    if (plan->d_stage) (void)hipFree(plan->d_stage);
-    if (plan->h_stage) (void)hipHostFree(plan->h_stage);
+    free_dev_stage(plan);
+    free_host_stage(plan);
     if (multipass && g_scratch_drawn.load() > 0) {
       (void)hipDeviceSynchronize();  // stream-ordered frees complete before the pool can let go of them
       trim_scratch_pools();

@@ -71,6 +71,16 @@ void trim_scratch_pools();
 // (PyTorch's, say) cannot see them, long after the last large transform.
 extern std::atomic<unsigned long long> g_scratch_drawn;
 
+// What the library holds right now, counted exactly (pdsp_dev_live_resources): touched where a table, a staging
+// buffer or a stream is created or freed and where a cached plan is evicted -- never on a launch path.
+struct LiveCounters {
+  std::atomic<long long> evictions{0};               // cached plans dropped to make room, since load
+  std::atomic<long long> tables{0}, table_bytes{0};  // upload_table minus Tables::release
+  std::atomic<long long> host_stage{0}, dev_stage{0};  // plans' pinned / device staging buffers
+  std::atomic<long long> streams{0};                 // plans' own streams and slot streams
+};
+extern LiveCounters g_live;
+
 struct StreamScratch {
   void *p = nullptr;
   hipStream_t s;
@@ -152,8 +162,11 @@ struct Tables {
   // every device allocation made for this precision, the lazily built win[] entries included (upload_table in
   // pdsp_capi.hip is the one place that adds to it).  Touched under plan->mu or before the plan is published only.
   std::vector<void *> owned;
+  size_t owned_bytes = 0;  // of `owned`, for the live counters
   void release() {
     for (void *p : owned) (void)hipFree(p);
+    pdsp_host::g_live.tables -= (long long)owned.size();
+    pdsp_host::g_live.table_bytes -= (long long)owned_bytes;
     *this = Tables{};
   }
 };

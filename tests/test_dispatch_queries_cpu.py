@@ -46,7 +46,7 @@ def test_header_and_ctypes_symbols_agree(pdsp):
         "pdsp_set_real_packed", "pdsp_set_istft_chunk_frames", "pdsp_set_upfirdn_tile", "pdsp_dev_upfirdn_tile",
         "pdsp_set_dwt_tile", "pdsp_dev_dwt_tile", "pdsp_dev_complex_op_vec4", "pdsp_dev_transform_path_f32",
         "pdsp_dev_transform_path_f64", "pdsp_dev_spectrum_path_f32", "pdsp_dev_spectrum_path_f64",
-        "pdsp_dev_host_transform_chunks", "pdsp_dev_host_spectrum_chunks"])
+        "pdsp_dev_host_transform_chunks", "pdsp_dev_host_spectrum_chunks", "pdsp_dev_live_resources"])
     assert not [s for s in header_symbols() if "_path_" in s]
     raw = C.CDLL(pdsp.LIB_PATH)
     for s in dev:
