@@ -145,7 +145,9 @@ PDSP_API int pdsp_plan_device(const pdsp_plan *plan);
  * N = 16384 f32 frames the cosine-sum window a0 - a1 cos(2 pi n/(N-1)) + a2 cos(4 pi n/(N-1)) is then
  * evaluated in registers (createWindow + applyWindow fused into the frame load; values agree with
  * the table to ~2e-7 absolute) instead of being re-read, 64 KB per frame, from L2.  Any other
- * pointer is used as a table of N values. */
+ * pointer is used as a table of N values.
+ * The first call for a type uploads the table with a synchronous allocation and copy, and the call takes no stream: a
+ * caller who captures a stream into a graph fetches the plan's windows before beginning the capture. */
 PDSP_API int pdsp_plan_window_f32(pdsp_plan *plan, int type, const float **window_out);
 PDSP_API int pdsp_plan_window_f64(pdsp_plan *plan, int type, const double **window_out);
 
@@ -566,7 +568,11 @@ PDSP_API long long pdsp_resampler_t0(const pdsp_resampler *rs);
 PDSP_API int pdsp_resampler_taps(const pdsp_resampler *rs, double *taps);
 /* full != 0: upfirdn's ((len - 1) up + ntaps - 1) / down + 1; else resample_poly's ceil(len up / down) */
 PDSP_API int pdsp_resample_output_len(const pdsp_resampler *rs, long long len, int full, long long *y_len);
-/* `batch` rows of `len` samples at x_stride -> rows of y_len outputs at y_stride (device pointers, any alignment) */
+/* `batch` rows of `len` samples at x_stride -> rows of y_len outputs at y_stride (device pointers, any alignment).
+ * The first call of a resampler in a precision uploads its tap table (synchronously); on a stream that is being captured
+ * that call is refused instead, before anything is allocated -- PDSP_ERR_BAD_ARG, "stream is capturing: ..." -- and the
+ * capture stays valid: make one call outside the capture first.  The same holds for the first call of a pdsp_dwt in a
+ * precision and of a pdsp_ntt. */
 PDSP_API int pdsp_upfirdn_f32(const pdsp_resampler *rs, long long batch, const float *x, long long len,
                               long long x_stride, float *y, long long y_len, long long y_stride, pdsp_stream stream);
 PDSP_API int pdsp_upfirdn_f64(const pdsp_resampler *rs, long long batch, const double *x, long long len,
@@ -702,7 +708,8 @@ PDSP_API int pdsp_wavelet_taps(const char *name, double *out, long long *ntaps);
 /* the deepest forward transform of rows of `len` values of elem_bytes (4 or 8) with ntaps taps: the largest J with
  * len mod 2^J == 0 that pdsp_dwt_forward_* takes; 0 for arguments outside the domain.  Needs no device. */
 PDSP_API int pdsp_dwt_max_levels(long long ntaps, long long len, int elem_bytes);
-/* `batch` rows of len samples at x_stride elements -> rows of len coefficients at y_stride elements, and back */
+/* `batch` rows of len samples at x_stride elements -> rows of len coefficients at y_stride elements, and back (the
+ * first call in a precision uploads the tap table: refused on a capturing stream, as pdsp_upfirdn_f32) */
 PDSP_API int pdsp_dwt_forward_f32(const pdsp_dwt *w, long long batch, const float *x, long long len,
                                   long long x_stride, float *y, long long y_stride, pdsp_stream stream);
 PDSP_API int pdsp_dwt_forward_f64(const pdsp_dwt *w, long long batch, const double *x, long long len,
@@ -741,7 +748,8 @@ typedef struct pdsp_ntt pdsp_ntt;
 PDSP_API int pdsp_ntt_create(long long n, int device, pdsp_ntt **out);
 PDSP_API int pdsp_ntt_destroy(pdsp_ntt *h);
 PDSP_API long long pdsp_ntt_size(const pdsp_ntt *h);
-/* `batch` rows of N values at in_stride elements -> rows of N values at out_stride elements */
+/* `batch` rows of N values at in_stride elements -> rows of N values at out_stride elements (a handle's first
+ * transform or convolution uploads its root table: refused on a capturing stream, as pdsp_upfirdn_f32) */
 PDSP_API int pdsp_ntt_forward_u64(const pdsp_ntt *h, long long batch, const uint64_t *in, long long in_stride,
                                   uint64_t *out, long long out_stride, pdsp_stream stream);
 PDSP_API int pdsp_ntt_inverse_u64(const pdsp_ntt *h, long long batch, const uint64_t *in, long long in_stride,

@@ -96,6 +96,12 @@ class BatchedFft(_device.Handle):
         if p is None:
             if kind not in _capi.WINDOW_TYPES:
                 raise PdspError(_capi.ERR_WINDOW_TYPE, f"Unsupported window type: {kind}")
+            # the first use uploads the table (a synchronous allocation and copy), which no capture allows; the
+            # library call has no stream to ask, so the refusal of pdsp_upfirdn_* and the others is made here
+            if torch.cuda.is_current_stream_capturing():
+                raise PdspError(_capi.ERR_BAD_ARG, f"stream is capturing: the {kind} window table is uploaded on its "
+                                                   "first use, which no capture allows; call plan.window"
+                                                   f"({kind!r}) once outside the capture first")
             out = C.c_void_p()
             check(getattr(lib, "pdsp_plan_window_" + self._sfx)(self._h, _capi.WINDOW_TYPES[kind], C.byref(out)))
             p = self._windows[kind] = out.value

@@ -291,6 +291,21 @@ hipError_t upload_table(Tables<T> &t, const std::vector<E> &host, D **out) {
   return hipSuccess;
 }
 
+// A table still to be uploaded on a caller's stream that is being captured: upload_table's hipMalloc and hipMemcpy are
+// synchronous, which a capture forbids, and either would invalidate the capture it ran into.  Asked only where the
+// table is missing and the stream is not the null stream; refused before anything is allocated or copied, so the capture
+// stays valid and the handle usable ("Streams and graphs").
+int refuse_upload_in_capture(hipStream_t s, const char *what) {
+  if (!s) return PDSP_OK;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  PDSP_HIP_TRY(hipStreamIsCapturing(s, &st));
+  if (st == hipStreamCaptureStatusNone) return PDSP_OK;
+  return fail(PDSP_ERR_BAD_ARG,
+              "stream is capturing: the %s is uploaded on the handle's first call in a precision, which no capture "
+              "allows; make one call on this handle outside the capture first",
+              what);
+}
+
 // Device copy of createWindow(type, N), built once per plan and precision (the window is
 // always computed in f64 on the host and rounded once).  Caller holds plan->mu.
 template <typename T>
@@ -2178,10 +2193,12 @@ int upfirdn_t(const pdsp_resampler *crs, long long batch, const T *x, long long 
     DeviceGuard dg(rs->device);
     PDSP_HIP_TRY(dg.err);
     T *&slot = resampler_table<T>(rs);
-    if (!slot)
+    if (!slot) {
+      if (int rc = refuse_upload_in_capture(s, "tap table")) return rc;
       if (hipError_t e = upload_table(resampler_owned<T>(rs), std::vector<T>(rs->g.begin(), rs->g.end()), &slot))
         return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the tap table", (int)e,
                     hipGetErrorString(e));
+    }
     g = slot;
   }
   DeviceGuard dg(rs->device);
@@ -2921,10 +2938,12 @@ int dwt_t(const pdsp_dwt *cw, bool inverse, long long batch, const T *in, long l
     DeviceGuard dg(w->device);
     PDSP_HIP_TRY(dg.err);
     T *&slot = dwt_table<T>(w);
-    if (!slot)
+    if (!slot) {
+      if (int rc = refuse_upload_in_capture(s, "tap table")) return rc;
       if (hipError_t e = upload_table(dwt_owned<T>(w), std::vector<T>(w->hg.begin(), w->hg.end()), &slot))
         return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the tap table", (int)e,
                     hipGetErrorString(e));
+    }
     hg = slot;
   }
   DeviceGuard dg(w->device);
@@ -3094,8 +3113,8 @@ int check_ntt_size(long long n) {
   return PDSP_OK;
 }
 
-// The handle's device and table for one call
-int ntt_table(pdsp_ntt *h, const uint64_t **tw) {
+// The handle's device and table for one call on stream s
+int ntt_table(pdsp_ntt *h, hipStream_t s, const uint64_t **tw) {
   if (int rc = require_device()) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   if (h->device < 0) PDSP_HIP_TRY(hipGetDevice(&h->device));
@@ -3103,6 +3122,7 @@ int ntt_table(pdsp_ntt *h, const uint64_t **tw) {
   PDSP_HIP_TRY(hipGetDeviceCount(&count));
   if (h->device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", h->device, count);
   if (!h->tw) {
+    if (int rc = refuse_upload_in_capture(s, "root table")) return rc;
     DeviceGuard dg(h->device);
     PDSP_HIP_TRY(dg.err);
     std::vector<uint64_t> w((size_t)h->n / 2);
@@ -3152,7 +3172,7 @@ int ntt_t(const pdsp_ntt *ch, int op, long long batch, const uint64_t *a, long l
     return fail(PDSP_ERR_BAD_ARG, conv ? "output overlaps an input (only out == a with equal strides may share bytes)"
                                        : "output overlaps input (only out == in with equal strides may share bytes)");
   const uint64_t *tw = nullptr;
-  if (int rc = ntt_table(h, &tw)) return rc;
+  if (int rc = ntt_table(h, s, &tw)) return rc;
   DeviceGuard dg(h->device);
   PDSP_HIP_TRY(dg.err);
   return ntt_dev(h->log2n, op, batch, a, a_stride, (int)a_len, b, b_stride, (int)b_len, out, out_stride, (int)out_len, tw,

@@ -75,7 +75,17 @@ class FirFilter:
             self._ready.record(torch.cuda.current_stream(self.device))
 
     def _wait_ready(self):
-        torch.cuda.current_stream(self.device).wait_event(self._ready)
+        """Orders the current stream behind the launch that wrote H, until that launch is known to have completed:
+        from then on a call enqueues its kernel and nothing else ("Streams and graphs").  The event is
+        never queried on a capturing stream."""
+        ready = self._ready  # read once: another thread may drop it meanwhile
+        if ready is None:
+            return
+        with torch.cuda.device(self.device):
+            if not torch.cuda.is_current_stream_capturing() and ready.query():
+                self._ready = None
+                return
+        torch.cuda.current_stream(self.device).wait_event(ready)
 
     def frequency_response(self):
         """H[k] = sum_j taps[j] e^{-2 pi i j k / N}, k = 0 ... N/2, as two device tensors (re, im), ordered on the
