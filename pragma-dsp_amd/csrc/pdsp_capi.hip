@@ -17,7 +17,9 @@
 #include <climits>
 #include <cstring>
 #include <atomic>
+#include <initializer_list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -480,6 +482,73 @@ int require_device() {
   return PDSP_OK;
 }
 
+// Which device a request means and whether it is visible: the current device for a negative request.  (Whether there is
+// a device at all is require_device()'s question, asked where each caller has always asked it.)
+int resolve_device(int *device) {
+  int count = 0;
+  PDSP_HIP_TRY(hipGetDeviceCount(&count));
+  if (*device < 0) PDSP_HIP_TRY(hipGetDevice(device));
+  if (*device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", *device, count);
+  return PDSP_OK;
+}
+
+// ---- handles that own device tables -------------------------------------------------------------------------
+// What the resampler, the DWT, the NTT, the sliding DFT and the chirp transforms share: a device, a lock, and the plans'
+// own lists of allocations -- 4-byte tables in t32, 8-byte tables in t64 (the NTT's uint64_t roots among them) -- filled
+// by upload_table and emptied by Tables::release, so a handle's tables are counted as a plan's are.  A handle adds what
+// is its own, with its per-precision pointers behind one slot<T>().
+struct TableHandle {
+  int device = -1;  // < 0 until the first device call: the device current then
+  std::mutex mu;    // the first-use upload; handles filled at create time never take it
+  Tables<float> t32;
+  Tables<double> t64;
+  template <typename T>
+  auto &owned() {
+    if constexpr (sizeof(T) == 4) return t32;
+    else return t64;
+  }
+};
+
+// The device and the table of one call on stream s, for the handles whose table goes up on the first call in a
+// precision (tap tables, root tables): under the handle's lock, the device resolved and current; where the slot is
+// still empty, build() makes the host copy and it is uploaded -- unless s is being captured.  The one place a rule
+// about lazy uploads has to be written.
+template <typename T, class Build>
+int first_use_table(TableHandle &h, T *&slot, hipStream_t s, const char *what, Build build) {
+  std::lock_guard<std::mutex> lk(h.mu);
+  if (int rc = resolve_device(&h.device)) return rc;
+  DeviceGuard dg(h.device);
+  PDSP_HIP_TRY(dg.err);
+  if (slot) return PDSP_OK;
+  if (int rc = refuse_upload_in_capture(s, what)) return rc;
+  if (hipError_t e = upload_table(h.owned<T>(), build(), &slot))
+    return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the %s", (int)e, hipGetErrorString(e),
+                what);
+  return PDSP_OK;
+}
+
+// A handle that owns no allocation (never used on a device, or its create failed at the first table) goes without a
+// single HIP call: such handles are made and destroyed on machines with no device.
+template <class H>
+int destroy_handle(H *h) {
+  if (!h) return PDSP_OK;
+  if (!h->t32.owned.empty() || !h->t64.owned.empty()) {
+    DeviceGuard g(h->device);
+    h->t32.release();
+    h->t64.release();
+  }
+  delete h;
+  return PDSP_OK;
+}
+
+// The handle a host form makes for one call, destroyed on every exit.
+template <class H>
+struct HandleDeleter {
+  void operator()(H *h) const { destroy_handle(h); }
+};
+template <class H>
+using HandleOwner = std::unique_ptr<H, HandleDeleter<H>>;
+
 // ---- chunked host calls -------------------------------------------------------------------------------------
 // A batched host-f64 call moves every sample through the CPU twice (the caller's f64 rows <-> pinned staging), over
 // PCIe twice, and through a kernel that needs a few percent of that time.  As ONE stage -> copy -> launch -> copy ->
@@ -565,6 +634,35 @@ inline bool host_ranges_overlap(const void *a, size_t a_bytes, const void *b, si
 inline bool mad_ok(long long a, long long b, long long c, long long *out) {
   long long p;
   return !__builtin_mul_overflow(a, b, &p) && !__builtin_add_overflow(p, c, out);
+}
+
+// One strided operand of a row call: rows of `len` elements, `stride` elements apart, `per_batch` of them for each row
+// of the call (the sliding DFT's series: one per bin).  *count receives its extent in elements, from the first element
+// of the first row to the last of the last: (rows - 1) * stride + len.
+struct RowExtent {
+  long long stride, len;
+  long long *count;
+  long long per_batch = 1;
+};
+// The extents of a call's operands, each of which must be computable and stay within LLONG_MAX / 8 elements, so that
+// its byte size in either precision is computable too.  A call of no rows has operands of no extent.
+int row_extents(long long batch, std::initializer_list<RowExtent> operands) {
+  for (const RowExtent &r : operands) {
+    long long rows = 0;
+    *r.count = 0;
+    if (batch > 0 && (!mad_ok(batch, r.per_batch, -1, &rows) || !mad_ok(rows, r.stride, r.len, r.count) ||
+                      *r.count > (LLONG_MAX / 8)))
+      return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  }
+  return PDSP_OK;
+}
+// The host forms' twin: batch contiguous rows of len values, at most 2^40 of them (the caller words the refusal).
+inline bool host_count_ok(long long batch, long long len, long long *count) {
+  return mad_ok(batch, len, 0, count) && *count <= (1LL << 40);
+}
+// The one overlap of an output with its input that the row kernels with an in-place form allow: the same rows.
+inline bool exact_in_place(const void *out, long long out_stride, const void *in, long long in_stride) {
+  return out == in && out_stride == in_stride;
 }
 
 // The element-wise kernels read index i of every input before they write index i and touch no other index, so an
@@ -1134,10 +1232,7 @@ int pdsp_plan_create(long long size, int device, pdsp_plan **plan_out) {
     return fail(PDSP_ERR_UNSUPPORTED_SIZE, "FFT size %lld exceeds the supported maximum %d", size,
                 1 << pdsp::kMaxLog2Big_f32);
   if (int rc = require_device()) return rc;
-  int count = 0;
-  PDSP_HIP_TRY(hipGetDeviceCount(&count));
-  if (device < 0) PDSP_HIP_TRY(hipGetDevice(&device));
-  if (device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", device, count);
+  if (int rc = resolve_device(&device)) return rc;
   DeviceGuard g(device);
   PDSP_HIP_TRY(g.err);
   pdsp_plan *p = new (std::nothrow) pdsp_plan();
@@ -1243,10 +1338,14 @@ int pdsp_planes_alloc(const pdsp_plan *plan, long long batch, int scalar_bytes, 
   *re_in = *im_in = *re_out = *im_out = nullptr;
   *arena = nullptr;
   if (arena_bytes) *arena_bytes = 0;
+  // a plane is batch contiguous rows: a batch no launch could take, or a size that does not compute, allocates nothing
+  long long count = 0;
+  if (int rc = check_plan_batch(plan, batch)) return rc;
+  if (int rc = row_extents(batch, {{plan->n, plan->n, &count}})) return rc;
   DeviceGuard g(plan->device);
   PDSP_HIP_TRY(g.err);
   const size_t gib = (size_t)1 << 30;
-  const size_t plane = (size_t)batch * (size_t)plan->n * (size_t)scalar_bytes;
+  const size_t plane = (size_t)count * (size_t)scalar_bytes;
   pdsp_arena *a = new (std::nothrow) pdsp_arena();
   if (!a) return fail(PDSP_ERR_BAD_ARG, "out of host memory");
   a->device = plan->device;
@@ -1626,19 +1725,17 @@ int fir_filter_t(const pdsp_plan *plan, long long batch, const T *x, long long l
   if (batch < 0 || len < 0 || y_off < 0 || y_len < 0)
     return fail(PDSP_ERR_BAD_ARG, "negative size (batch %lld, len %lld, y_off %lld, y_len %lld)", batch, len, y_off, y_len);
   if (x_stride < 0 || y_stride < 0) return fail(PDSP_ERR_BAD_ARG, "negative stride");
-  long long full = 0, last = 0;
+  long long full = 0, xc = 0, yc = 0;
   if (__builtin_add_overflow(len, ntaps - 1, &full) || y_off > full || y_len > full - y_off)
     return fail(PDSP_ERR_BAD_ARG, "outputs [%lld, %lld + %lld) beyond the full convolution of %lld samples", y_off, y_off,
                 y_len, full);
   if (batch > 1 && y_stride < y_len) return fail(PDSP_ERR_BAD_ARG, "y_stride %lld < y_len %lld", y_stride, y_len);
-  if (batch > 0 && (!mad_ok(batch - 1, x_stride, len, &last) || !mad_ok(batch - 1, y_stride, y_len, &last)))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (int rc = row_extents(batch, {{x_stride, len, &xc}, {y_stride, y_len, &yc}})) return rc;
   if (batch == 0 || y_len == 0) return PDSP_OK;
   if (!y || (len > 0 && (!x || !h_re || !h_im))) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   // blocks of a row read input that other blocks overwrite when y shares bytes with x: the result would depend on
   // the order in which workgroups run.  Byte ranges of the whole strided extent, as planes_overlap()
-  if (len > 0 && host_ranges_overlap(x, (size_t)((batch - 1) * x_stride + len) * sizeof(T), y,
-                                     (size_t)((batch - 1) * y_stride + y_len) * sizeof(T)))
+  if (len > 0 && host_ranges_overlap(x, (size_t)xc * sizeof(T), y, (size_t)yc * sizeof(T)))
     return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
   // an even filter runs with one zero tap more (same H): P odd makes hop = N - P + 1 even, the aligned fast path
   const int p = (int)(ntaps % 2 == 1 ? ntaps : ntaps + 1);
@@ -1717,7 +1814,7 @@ int pdsp_fir_filter_host_f64(const double *x, long long batch, long long len, co
     return fail(PDSP_ERR_UNSUPPORTED_SIZE, "filter of %lld taps exceeds N/2 = 8192 of the largest block (no partitioned convolution)",
                 ntaps);
   long long xs = 0, ys = 0;
-  if (!mad_ok(batch, len, 0, &xs) || !mad_ok(batch, y_len, 0, &ys) || xs > (1LL << 40) || ys > (1LL << 40))
+  if (!host_count_ok(batch, len, &xs) || !host_count_ok(batch, y_len, &ys))
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x length overflows", batch);
   if (batch == 0) return PDSP_OK;
   if (!x || !taps || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
@@ -1752,9 +1849,7 @@ int stft_complex_t(const pdsp_plan *plan, long long batch, const T *frames, long
   if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
   const long long n = plan->n, bins = n / 2 + 1, used = frame_len < n ? frame_len : n;
   long long in_count = 0, out_count = 0;
-  if (!mad_ok(batch - 1, frame_stride, used, &in_count) || !mad_ok(batch, bins, 0, &out_count) ||
-      in_count > (LLONG_MAX / 8) || out_count > (LLONG_MAX / 8))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (int rc = row_extents(batch, {{frame_stride, used, &in_count}, {bins, bins, &out_count}})) return rc;
   if (!frames || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   const size_t ib = (size_t)in_count * sizeof(T), ob = (size_t)out_count * sizeof(T), wb = (size_t)n * sizeof(T);
   if (host_ranges_overlap(re_out, ob, frames, ib) || host_ranges_overlap(im_out, ob, frames, ib) ||
@@ -1848,8 +1943,8 @@ int pdsp_istft_host_f64(const double *re, const double *im, long long frames, lo
   if (frames < 1) return fail(PDSP_ERR_BAD_ARG, "frames must be >= 1, got %lld", frames);
   const long long bins = fft_size / 2 + 1;
   long long total = 0, in_count = 0;
-  if (frames > 0x7fffffffLL || !mad_ok(frames - 1, hop, fft_size, &total) || !mad_ok(frames, bins, 0, &in_count) ||
-      total > (1LL << 40) || in_count > (1LL << 40))
+  if (frames > 0x7fffffffLL || !mad_ok(frames - 1, hop, fft_size, &total) || total > (1LL << 40) ||
+      !host_count_ok(frames, bins, &in_count))
     return fail(PDSP_ERR_BAD_ARG, "frames %lld x hop %lld overflows", frames, hop);
   if (!re || !im || !out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   const size_t nin = (size_t)in_count, ny = (size_t)total;  // buffer: re | im | signal
@@ -1901,15 +1996,12 @@ int dct_t(const pdsp_plan *plan, long long batch, const T *x, long long x_stride
     return fail(PDSP_ERR_BAD_ARG, "strides must be >= N = %lld, got x_stride %lld, y_stride %lld", n, x_stride, y_stride);
   if (int rc = check_dct_type_norm(type, norm)) return rc;
   long long xc = 0, yc = 0;
-  if (!mad_ok(batch - 1, x_stride, n, &xc) || !mad_ok(batch - 1, y_stride, n, &yc) || xc > (LLONG_MAX / 8) ||
-      yc > (LLONG_MAX / 8))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (int rc = row_extents(batch, {{x_stride, n, &xc}, {y_stride, n, &yc}})) return rc;
   if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
   if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   // exact in place is safe (each row is loaded in full by its own workgroup before that workgroup's first barrier);
   // any other overlap would let one row's stores reach another row's loads
-  const bool in_place = (const void *)x == (const void *)y && x_stride == y_stride;
-  if (!in_place && host_ranges_overlap(y, (size_t)yc * sizeof(T), x, (size_t)xc * sizeof(T)))
+  if (!exact_in_place(y, y_stride, x, x_stride) && host_ranges_overlap(y, (size_t)yc * sizeof(T), x, (size_t)xc * sizeof(T)))
     return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only y == x with y_stride == x_stride may share bytes)");
   double g = 1.0, g0 = 1.0;
   dct_scales(n, type, norm, &g, &g0);
@@ -1934,7 +2026,7 @@ int pdsp_dct_host_f64(const double *x, long long batch, long long n, int type, i
   if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
   if (int rc = check_dct_type_norm(type, norm)) return rc;
   long long count = 0;
-  if (batch > 0x7fffffffLL || !mad_ok(batch, n, 0, &count) || count > (1LL << 40))
+  if (batch > 0x7fffffffLL || !host_count_ok(batch, n, &count))
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x %lld overflows", batch, n);
   if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   const size_t nx = (size_t)count;
@@ -1974,16 +2066,13 @@ int hilbert_t(const pdsp_plan *plan, long long batch, const T *x, long long x_st
     return fail(PDSP_ERR_BAD_ARG, "strides must be >= len = %lld (x) and >= %lld (y), got x_stride %lld, y_stride %lld",
                 len, yn, x_stride, y_stride);
   long long xc = 0, yc = 0;
-  if (!mad_ok(batch - 1, x_stride, len, &xc) || !mad_ok(batch - 1, y_stride, yn, &yc) || xc > (LLONG_MAX / 8) ||
-      yc > (LLONG_MAX / 8))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (int rc = row_extents(batch, {{x_stride, len, &xc}, {y_stride, yn, &yc}})) return rc;
   if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
   if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   // exact in place is safe in the N-out modes (a row is loaded in full by its own workgroup before that workgroup's
   // first barrier, and a thread stores only to the samples it has just re-read); any other overlap would let one
   // row's stores reach another row's loads, and ANALYTIC writes two values per sample
-  const bool in_place =
-      out_mode != PDSP_HILBERT_ANALYTIC && (const void *)x == (const void *)y && x_stride == y_stride;
+  const bool in_place = out_mode != PDSP_HILBERT_ANALYTIC && exact_in_place(y, y_stride, x, x_stride);
   if (!in_place && host_ranges_overlap(y, (size_t)yc * sizeof(T), x, (size_t)xc * sizeof(T)))
     return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only y == x with y_stride == x_stride may share bytes, and "
                                   "not in analytic mode)");
@@ -2010,7 +2099,7 @@ int pdsp_hilbert_host_f64(const double *x, long long batch, long long len, long 
   if (int rc = check_hilbert_mode(out_mode)) return rc;
   const long long yn = out_mode == PDSP_HILBERT_ANALYTIC ? 2 * n : n;
   long long xcount = 0, ycount = 0;
-  if (batch > 0x7fffffffLL || !mad_ok(batch, len, 0, &xcount) || !mad_ok(batch, yn, 0, &ycount) || ycount > (1LL << 40))
+  if (batch > 0x7fffffffLL || !host_count_ok(batch, len, &xcount) || !host_count_ok(batch, yn, &ycount))
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x %lld overflows", batch, n);
   if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   // buffer: y | x, rows of n values on the device whatever len is (the wide path's layout)
@@ -2032,17 +2121,18 @@ int pdsp_hilbert_host_f64(const double *x, long long batch, long long len, long 
 
 // A resampler is its tap table: no FFT size, so no plan.  The table is kept in f64, phase-major
 // (g[p][j] = h[p + j up], up rows of T = ceil(ntaps / up), zero-padded), rounded once per precision and uploaded on
-// first use -- the rule of the plans' tables, through the same uploader and the same owned list.
-struct pdsp_resampler {
-  int device = -1;  // < 0 until the first device call: the device current then
+// first use (TableHandle, first_use_table).
+struct pdsp_resampler : TableHandle {
   long long up = 1, down = 1, ntaps = 1, t0 = 0;
   std::vector<double> taps;  // as convolved (resample_poly: times up)
   std::vector<double> g;
-  std::mutex mu;
-  Tables<float> t32;
-  Tables<double> t64;
   float *g32 = nullptr;
   double *g64 = nullptr;
+  template <typename T>
+  auto &slot() {
+    if constexpr (sizeof(T) == 4) return g32;
+    else return g64;
+  }
 };
 
 namespace pdsp_host {
@@ -2145,13 +2235,6 @@ int resample_poly_setup(long long up, long long down, const double *taps, long l
   return PDSP_OK;
 }
 
-template <typename T> T *&resampler_table(pdsp_resampler *rs);
-template <> float *&resampler_table<float>(pdsp_resampler *rs) { return rs->g32; }
-template <> double *&resampler_table<double>(pdsp_resampler *rs) { return rs->g64; }
-template <typename T> Tables<T> &resampler_owned(pdsp_resampler *rs);
-template <> Tables<float> &resampler_owned<float>(pdsp_resampler *rs) { return rs->t32; }
-template <> Tables<double> &resampler_owned<double>(pdsp_resampler *rs) { return rs->t64; }
-
 int resample_len(const pdsp_resampler *rs, long long len, int full, long long *y_len) {
   if (len < 1) return fail(PDSP_ERR_BAD_ARG, "len must be >= 1, got %lld", len);
   long long v = 0;
@@ -2172,9 +2255,7 @@ int upfirdn_t(const pdsp_resampler *crs, long long batch, const T *x, long long 
     return fail(PDSP_ERR_BAD_ARG, "strides must be >= len = %lld (x) and >= y_len = %lld (y), got x_stride %lld, y_stride %lld",
                 len, y_len, x_stride, y_stride);
   long long xc = 0, yc = 0, q = 0;
-  if (batch > 0 && (!mad_ok(batch - 1, x_stride, len, &xc) || !mad_ok(batch - 1, y_stride, y_len, &yc) ||
-                    xc > (LLONG_MAX / 8) || yc > (LLONG_MAX / 8)))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (int rc = row_extents(batch, {{x_stride, len, &xc}, {y_stride, y_len, &yc}})) return rc;
   if (!mad_ok(y_len, rs->down, rs->t0 + rs->up * rs->down, &q))
     return fail(PDSP_ERR_BAD_ARG, "y_len %lld x down %lld overflows", y_len, rs->down);
   if (batch == 0 || y_len == 0) return PDSP_OK;
@@ -2183,24 +2264,9 @@ int upfirdn_t(const pdsp_resampler *crs, long long batch, const T *x, long long 
   if (host_ranges_overlap(x, (size_t)xc * sizeof(T), y, (size_t)yc * sizeof(T)))
     return fail(PDSP_ERR_BAD_ARG, "output overlaps input");
   if (int rc = require_device()) return rc;
-  T *g = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(rs->mu);
-    if (rs->device < 0) PDSP_HIP_TRY(hipGetDevice(&rs->device));
-    int count = 0;
-    PDSP_HIP_TRY(hipGetDeviceCount(&count));
-    if (rs->device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", rs->device, count);
-    DeviceGuard dg(rs->device);
-    PDSP_HIP_TRY(dg.err);
-    T *&slot = resampler_table<T>(rs);
-    if (!slot) {
-      if (int rc = refuse_upload_in_capture(s, "tap table")) return rc;
-      if (hipError_t e = upload_table(resampler_owned<T>(rs), std::vector<T>(rs->g.begin(), rs->g.end()), &slot))
-        return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the tap table", (int)e,
-                    hipGetErrorString(e));
-    }
-    g = slot;
-  }
+  T *&g = rs->slot<T>();
+  if (int rc = first_use_table(*rs, g, s, "tap table", [&] { return std::vector<T>(rs->g.begin(), rs->g.end()); }))
+    return rc;
   DeviceGuard dg(rs->device);
   PDSP_HIP_TRY(dg.err);
   return upfirdn_dev<T>(g, rs->up, rs->down, rs->ntaps, rs->t0, batch, x, len, x_stride, y, y_len, y_stride, s);
@@ -2209,14 +2275,11 @@ int upfirdn_t(const pdsp_resampler *crs, long long batch, const T *x, long long 
 // The host forms: one resampler, one device buffer x | y, the f64 kernel on the null stream (pdsp_fir_filter_host_f64's
 // shape: f64 arithmetic whatever pdsp_set_host_precision says).
 int resample_host(pdsp_resampler *rs, const double *x, long long batch, long long len, int full, double *y) {
-  struct Owner {
-    pdsp_resampler *p;
-    ~Owner() { pdsp_resampler_destroy(p); }
-  } own{rs};
+  const HandleOwner<pdsp_resampler> own(rs);
   if (batch < 0) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 0, got %lld", batch);
   long long y_len = 0, xs = 0, ys = 0;
   if (int rc = resample_len(rs, len, full, &y_len)) return rc;
-  if (!mad_ok(batch, len, 0, &xs) || !mad_ok(batch, y_len, 0, &ys) || xs > (1LL << 40) || ys > (1LL << 40))
+  if (!host_count_ok(batch, len, &xs) || !host_count_ok(batch, y_len, &ys))
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x length overflows", batch);
   if (batch == 0) return PDSP_OK;
   if (!x || !y) return fail(PDSP_ERR_BAD_ARG, "null buffer");
@@ -2254,16 +2317,7 @@ int pdsp_resampler_create_poly(int device, long long up, long long down, const d
   return resampler_new(device, up, down, std::move(h), t0, out);
 }
 
-int pdsp_resampler_destroy(pdsp_resampler *rs) {
-  if (!rs) return PDSP_OK;
-  if (rs->g32 || rs->g64) {
-    DeviceGuard g(rs->device);
-    rs->t32.release();
-    rs->t64.release();
-  }
-  delete rs;
-  return PDSP_OK;
-}
+int pdsp_resampler_destroy(pdsp_resampler *rs) { return destroy_handle(rs); }
 
 long long pdsp_resampler_up(const pdsp_resampler *rs) { return rs ? rs->up : 0; }
 long long pdsp_resampler_down(const pdsp_resampler *rs) { return rs ? rs->down : 0; }
@@ -2407,21 +2461,20 @@ namespace pdsp_host {
 // A chirp-z transform of L samples into K bins is its three tables -- pre[n] = a^-n w^(n^2/2), post[k] = w^(k^2/2) and
 // Bt = FFT_M(b) / M of the chirp filter b[j] = w^(-j^2/2) -- evaluated on the host and rounded once per precision, plus
 // the radix table of the M-point transform (the tw_half of a plan of 2M points).  They go up at create time through the
-// plans' uploader into the object's own lists.  A DFT is the transform with K = L whose post is its pre, the chirp
-// c[n] = exp(-i pi n^2 / L), uploaded once.
+// plans' uploader into the handle's own lists (TableHandle).  A DFT is the transform with K = L whose post is its pre,
+// the chirp c[n] = exp(-i pi n^2 / L), uploaded once.
 template <typename T>
 struct ChirpSet {
-  Tables<T> t;  // tw_half: the M-point radix table; owned: every allocation of this precision
+  typename pdsp::vec2<T>::type *tw = nullptr;  // the M-point radix table
   typename pdsp::vec2<T>::type *pre = nullptr, *post = nullptr, *bt = nullptr;
 };
-struct ChirpTables {
-  int device = -1;
+struct ChirpTables : TableHandle {
   long long length = 0, bins = 0, m = 0;
   int log2m = 0;
   ChirpSet<float> s32;
   ChirpSet<double> s64;
   template <typename T>
-  const ChirpSet<T> &set() const {
+  const ChirpSet<T> &slot() const {
     if constexpr (sizeof(T) == 4) return s32;
     else return s64;
   }
@@ -2477,46 +2530,30 @@ std::vector<T2> chirp_round(const std::vector<double2> &v) {
   return r;
 }
 
-template <class H>
-int chirp_destroy(H *h) {
-  if (!h) return PDSP_OK;
-  {
-    DeviceGuard g(h->device);
-    h->s32.t.release();
-    h->s64.t.release();
-  }
-  delete h;
-  return PDSP_OK;
-}
-
 // The object of one transform on `device` (< 0: the current one), behind its creator's own argument checks: its
 // tables in both precisions.  post null: the DFT, whose post is its pre.  what: the transform's name in the message.
 template <class H>
 int chirp_create(H **out, const char *what, int device, long long length, long long bins,
                  const std::vector<double2> &pre, const std::vector<double2> *post, const std::vector<double2> &bt) {
   if (int rc = require_device()) return rc;
-  int count = 0;
-  PDSP_HIP_TRY(hipGetDeviceCount(&count));
-  if (device < 0) PDSP_HIP_TRY(hipGetDevice(&device));
-  if (device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", device, count);
+  if (int rc = resolve_device(&device)) return rc;
   DeviceGuard g(device);
   PDSP_HIP_TRY(g.err);
   H *h = new (std::nothrow) H();
   if (!h) return fail(PDSP_ERR_BAD_ARG, "out of host memory");
   h->device = device, h->length = length, h->bins = bins, h->log2m = chirp_log2m(length, bins), h->m = 1LL << h->log2m;
-  auto upload = [&](auto &s) -> hipError_t {
+  auto upload = [&](auto &t, auto &s) -> hipError_t {
     using T2 = std::remove_pointer_t<decltype(s.pre)>;
-    if (hipError_t e = upload_table(s.t, build_twiddles<T2>(h->log2m, pdsp::packed_log2e(h->log2m)), &s.t.tw_half))
-      return e;
-    if (hipError_t e = upload_table(s.t, chirp_round<T2>(pre), &s.pre)) return e;
+    if (hipError_t e = upload_table(t, build_twiddles<T2>(h->log2m, pdsp::packed_log2e(h->log2m)), &s.tw)) return e;
+    if (hipError_t e = upload_table(t, chirp_round<T2>(pre), &s.pre)) return e;
     if (!post) s.post = s.pre;
-    else if (hipError_t e = upload_table(s.t, chirp_round<T2>(*post), &s.post)) return e;
-    return upload_table(s.t, chirp_round<T2>(bt), &s.bt);
+    else if (hipError_t e = upload_table(t, chirp_round<T2>(*post), &s.post)) return e;
+    return upload_table(t, chirp_round<T2>(bt), &s.bt);
   };
-  hipError_t e = upload(h->s32);
-  if (e == hipSuccess) e = upload(h->s64);
+  hipError_t e = upload(h->t32, h->s32);
+  if (e == hipSuccess) e = upload(h->t64, h->s64);
   if (e != hipSuccess) {
-    chirp_destroy(h);
+    destroy_handle(h);
     return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the %s tables", (int)e,
                 hipGetErrorString(e), what);
   }
@@ -2541,13 +2578,11 @@ int chirp_t(const ChirpTables &c, int dft, long long batch, const T *re_in, cons
     return fail(PDSP_ERR_BAD_ARG, "strides must be >= L = %lld in and >= K = %lld out, got in_stride %lld, out_stride %lld",
                 n, k, in_stride, out_stride);
   long long ic = 0, oc = 0;
-  if (!mad_ok(batch - 1, in_stride, n, &ic) || !mad_ok(batch - 1, out_stride, k, &oc) || ic > (LLONG_MAX / 8) ||
-      oc > (LLONG_MAX / 8))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (int rc = row_extents(batch, {{in_stride, n, &ic}, {out_stride, k, &oc}})) return rc;
   if (batch > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
   if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   const size_t ib = (size_t)ic * sizeof(T), ob = (size_t)oc * sizeof(T), xb = ib > ob ? ib : ob;
-  const bool in_place = (const void *)re_out == (const void *)re_in && in_stride == out_stride &&
+  const bool in_place = exact_in_place(re_out, out_stride, re_in, in_stride) &&
                         (im_in ? (const void *)im_out == (const void *)im_in : !dft);
   const bool clash = !in_place ? (host_ranges_overlap(re_out, ob, re_in, ib) || host_ranges_overlap(re_out, ob, im_in, ib) ||
                                   host_ranges_overlap(im_out, ob, re_in, ib) || host_ranges_overlap(im_out, ob, im_in, ib))
@@ -2559,14 +2594,14 @@ int chirp_t(const ChirpTables &c, int dft, long long batch, const T *re_in, cons
                                   "may share bytes)", dft ? "" : " -- a real row's im_out apart --");
   if (host_ranges_overlap(re_out, ob, im_out, ob))
     return fail(PDSP_ERR_BAD_ARG, "the output planes overlap each other");
-  const ChirpSet<T> &v = c.set<T>();
+  const ChirpSet<T> &v = c.slot<T>();
   DeviceGuard dg(c.device);
   PDSP_HIP_TRY(dg.err);
   if (dft)
-    return dft_dev<T>(c.log2m, n, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, v.pre, v.bt, v.t.tw_half,
+    return dft_dev<T>(c.log2m, n, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, v.pre, v.bt, v.tw,
                       dft < 0, s);
-  return czt_dev<T>(c.log2m, n, k, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, v.pre, v.post, v.bt,
-                    v.t.tw_half, s);
+  return czt_dev<T>(c.log2m, n, k, batch, re_in, im_in, in_stride, re_out, im_out, out_stride, v.pre, v.post, v.bt, v.tw,
+                    s);
 }
 
 // The host forms ride the packed features' scaffold on the cached plan of 2M points (64 ... 16384: its stream, its
@@ -2577,23 +2612,21 @@ int chirp_host(int dft, const double *re_in, const double *im_in, long long batc
                double *re_out, double *im_out, Create create) {
   if (batch < 1) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 1, got %lld", batch);
   long long cin = 0, cout = 0;
-  if (batch > 0x7fffffffLL || !mad_ok(batch, length, 0, &cin) || !mad_ok(batch, bins, 0, &cout) || cin > (1LL << 40) ||
-      cout > (1LL << 40))
+  if (batch > 0x7fffffffLL || !host_count_ok(batch, length, &cin) || !host_count_ok(batch, bins, &cout))
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x (%lld, %lld) overflows", batch, length, bins);
   if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   const size_t nx = (size_t)cin, ny = (size_t)cout;
-  struct Owner {
-    H *p = nullptr;
-    ~Owner() { chirp_destroy(p); }
-  } own;
+  HandleOwner<H> own;
   return packed_host_call(
       2LL << chirp_log2m(length, bins), PDSP_WIN_RECT, 2 * ny + 2 * nx,
       [&](pdsp_plan *plan, hipStream_t s, const double *, double *d) -> int {
-        if (int rc = create(plan->device, &own.p)) return rc;
+        H *h = nullptr;
+        if (int rc = create(plan->device, &h)) return rc;
+        own.reset(h);
         double *const xr = d + 2 * ny, *const xi = xr + nx;
         PDSP_HIP_TRY(hipMemcpyAsync(xr, re_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
         if (im_in) PDSP_HIP_TRY(hipMemcpyAsync(xi, im_in, nx * sizeof(double), hipMemcpyHostToDevice, s));
-        return chirp_t<double>(*own.p, dft, batch, xr, im_in ? xi : nullptr, length, d, d + ny, bins, s);
+        return chirp_t<double>(*own, dft, batch, xr, im_in ? xi : nullptr, length, d, d + ny, bins, s);
       },
       [&](const double *d) -> int {
         PDSP_HIP_TRY(hipMemcpy(re_out, d, ny * sizeof(double), hipMemcpyDeviceToHost));
@@ -2732,7 +2765,7 @@ int pdsp_dft_create(long long length, int device, pdsp_dft **out) {
                       dft_filter_spectrum(c, chirp_log2m(length, length)));
 }
 
-int pdsp_dft_destroy(pdsp_dft *d) { return chirp_destroy(d); }
+int pdsp_dft_destroy(pdsp_dft *d) { return destroy_handle(d); }
 long long pdsp_dft_length(const pdsp_dft *d) { return d ? d->length : 0; }
 long long pdsp_dft_conv_size(const pdsp_dft *d) { return d ? d->m : 0; }
 
@@ -2761,7 +2794,7 @@ int pdsp_czt_create(long long length, long long bins, double step, double start,
                       czt_filter_spectrum(length, bins, step, chirp_log2m(length, bins)));
 }
 
-int pdsp_czt_destroy(pdsp_czt *c) { return chirp_destroy(c); }
+int pdsp_czt_destroy(pdsp_czt *c) { return destroy_handle(c); }
 long long pdsp_czt_length(const pdsp_czt *c) { return c ? c->length : 0; }
 long long pdsp_czt_bins(const pdsp_czt *c) { return c ? c->bins : 0; }
 long long pdsp_czt_conv_size(const pdsp_czt *c) { return c ? c->m : 0; }
@@ -2786,17 +2819,17 @@ int pdsp_czt_host_f64(const double *re_in, const double *im_in, long long batch,
 /* ---- multi-level wavelet transform: wavedec / waverec -------------------------- */
 
 // A wavelet transform is its scaling filter and its depth: no FFT size, so no plan.  The taps are kept in f64, h | g,
-// rounded once per precision and uploaded on first use -- the rule of the plans' tables, through the same uploader and
-// the same owned list.
-struct pdsp_dwt {
-  int device = -1;  // < 0 until the first device call: the device current then
+// rounded once per precision and uploaded on first use (TableHandle, first_use_table).
+struct pdsp_dwt : TableHandle {
   int levels = 1;
   std::vector<double> hg;  // h | g, g[j] = (-1)^j h[F - 1 - j]
-  std::mutex mu;
-  Tables<float> t32;
-  Tables<double> t64;
   float *hg32 = nullptr;
   double *hg64 = nullptr;
+  template <typename T>
+  auto &slot() {
+    if constexpr (sizeof(T) == 4) return hg32;
+    else return hg64;
+  }
 };
 
 namespace pdsp_host {
@@ -2892,13 +2925,6 @@ int check_dwt_len(long long len, int levels) {
   return PDSP_OK;
 }
 
-template <typename T> T *&dwt_table(pdsp_dwt *w);
-template <> float *&dwt_table<float>(pdsp_dwt *w) { return w->hg32; }
-template <> double *&dwt_table<double>(pdsp_dwt *w) { return w->hg64; }
-template <typename T> Tables<T> &dwt_owned(pdsp_dwt *w);
-template <> Tables<float> &dwt_owned<float>(pdsp_dwt *w) { return w->t32; }
-template <> Tables<double> &dwt_owned<double>(pdsp_dwt *w) { return w->t64; }
-
 template <typename T>
 int dwt_t(const pdsp_dwt *cw, bool inverse, long long batch, const T *in, long long len, long long in_stride, T *out,
           long long out_stride, hipStream_t s) {
@@ -2911,9 +2937,7 @@ int dwt_t(const pdsp_dwt *cw, bool inverse, long long batch, const T *in, long l
     return fail(PDSP_ERR_BAD_ARG, "strides must be >= len = %lld, got %lld (input) and %lld (output)", len, in_stride,
                 out_stride);
   long long ic = 0, oc = 0;
-  if (batch > 0 && (!mad_ok(batch - 1, in_stride, len, &ic) || !mad_ok(batch - 1, out_stride, len, &oc) ||
-                    ic > (LLONG_MAX / 8) || oc > (LLONG_MAX / 8)))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (int rc = row_extents(batch, {{in_stride, len, &ic}, {out_stride, len, &oc}})) return rc;
   if (batch == 0) return PDSP_OK;
   if (!in || !out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   DwtTile t;
@@ -2923,29 +2947,14 @@ int dwt_t(const pdsp_dwt *cw, bool inverse, long long batch, const T *in, long l
     return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld rows of %lld tiles", batch, t.tiles);
   // resident: a workgroup loads its whole row before it stores anything, so the exact in-place call is safe.  Any other
   // overlap lets one workgroup's stores reach another's loads: byte ranges of the whole strided extents
-  const bool in_place = t.resident && (const void *)out == (const void *)in && in_stride == out_stride;
+  const bool in_place = t.resident && exact_in_place(out, out_stride, in, in_stride);
   if (!in_place && host_ranges_overlap(in, (size_t)ic * sizeof(T), out, (size_t)oc * sizeof(T)))
     return fail(PDSP_ERR_BAD_ARG, t.resident ? "output overlaps input (only out == in with equal strides may share bytes)"
                                              : "output overlaps input (rows beyond the resident path share no bytes)");
   if (int rc = require_device()) return rc;
-  T *hg = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(w->mu);
-    if (w->device < 0) PDSP_HIP_TRY(hipGetDevice(&w->device));
-    int count = 0;
-    PDSP_HIP_TRY(hipGetDeviceCount(&count));
-    if (w->device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", w->device, count);
-    DeviceGuard dg(w->device);
-    PDSP_HIP_TRY(dg.err);
-    T *&slot = dwt_table<T>(w);
-    if (!slot) {
-      if (int rc = refuse_upload_in_capture(s, "tap table")) return rc;
-      if (hipError_t e = upload_table(dwt_owned<T>(w), std::vector<T>(w->hg.begin(), w->hg.end()), &slot))
-        return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the tap table", (int)e,
-                    hipGetErrorString(e));
-    }
-    hg = slot;
-  }
+  T *&hg = w->slot<T>();
+  if (int rc = first_use_table(*w, hg, s, "tap table", [&] { return std::vector<T>(w->hg.begin(), w->hg.end()); }))
+    return rc;
   DeviceGuard dg(w->device);
   PDSP_HIP_TRY(dg.err);
   return dwt_dev<T>(t, hg, (int)f, w->levels, inverse, batch, in, len, in_stride, out, out_stride, s);
@@ -2955,26 +2964,23 @@ int dwt_t(const pdsp_dwt *cw, bool inverse, long long batch, const T *in, long l
 // device); the transform's own object lives for the call.  Buffer: out | in.
 int dwt_host(bool inverse, const double *in, long long batch, long long len, const char *name, const double *taps,
              long long ntaps, int levels, double *out) {
-  struct Owner {
-    pdsp_dwt *p = nullptr;
-    ~Owner() { pdsp_dwt_destroy(p); }
-  } own;
-  if (int rc = pdsp_dwt_create(-1, name, taps, ntaps, levels, &own.p)) return rc;
+  pdsp_dwt *w = nullptr;
+  if (int rc = pdsp_dwt_create(-1, name, taps, ntaps, levels, &w)) return rc;
+  const HandleOwner<pdsp_dwt> own(w);
   if (batch < 0) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 0, got %lld", batch);
   if (int rc = check_dwt_len(len, levels)) return rc;
   long long count = 0;
-  if (!mad_ok(batch, len, 0, &count) || count > (1LL << 40))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x length overflows", batch);
+  if (!host_count_ok(batch, len, &count)) return fail(PDSP_ERR_BAD_ARG, "batch %lld x length overflows", batch);
   if (batch == 0) return PDSP_OK;
   if (!in || !out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   DwtTile t;
-  if (int rc = dwt_tile_checked((long long)own.p->hg.size() / 2, levels, len, sizeof(double), inverse, &t)) return rc;
+  if (int rc = dwt_tile_checked((long long)w->hg.size() / 2, levels, len, sizeof(double), inverse, &t)) return rc;
   const size_t nx = (size_t)count;
   return packed_host_call(
       64, PDSP_WIN_RECT, 2 * nx,
       [&](pdsp_plan *, hipStream_t s, const double *, double *d) -> int {
         PDSP_HIP_TRY(hipMemcpyAsync(d + nx, in, nx * sizeof(double), hipMemcpyHostToDevice, s));
-        return dwt_t<double>(own.p, inverse, batch, d + nx, len, len, d, len, s);
+        return dwt_t<double>(w, inverse, batch, d + nx, len, len, d, len, s);
       },
       [&](const double *d) -> int {
         PDSP_HIP_TRY(hipMemcpy(out, d, nx * sizeof(double), hipMemcpyDeviceToHost));
@@ -3013,16 +3019,7 @@ int pdsp_dwt_create(int device, const char *name_or_null, const double *taps_or_
   return PDSP_OK;
 }
 
-int pdsp_dwt_destroy(pdsp_dwt *w) {
-  if (!w) return PDSP_OK;
-  if (w->hg32 || w->hg64) {
-    DeviceGuard g(w->device);
-    w->t32.release();
-    w->t64.release();
-  }
-  delete w;
-  return PDSP_OK;
-}
+int pdsp_dwt_destroy(pdsp_dwt *w) { return destroy_handle(w); }
 
 long long pdsp_dwt_ntaps(const pdsp_dwt *w) { return w ? (long long)w->hg.size() / 2 : 0; }
 int pdsp_dwt_levels(const pdsp_dwt *w) { return w ? w->levels : 0; }
@@ -3092,14 +3089,11 @@ int pdsp_dev_dwt_tile(long long ntaps, int levels, long long len, int elem_bytes
 
 // ---- number-theoretic transform and exact convolution over GF(2^64 - 2^32 + 1) ---------------------------------
 // A handle is its size and the table omega_N^j, j < N / 2, built on the host with the header the kernels compute with
-// and uploaded on first use -- the rule of the plans' tables, through the same uploader and the same owned list.
+// and uploaded on first use (TableHandle, first_use_table: one precision, so one slot, in the 8-byte list).
 
-struct pdsp_ntt {
+struct pdsp_ntt : TableHandle {
   long long n = 0;
   int log2n = 0;
-  int device = -1;  // < 0 until the first device call: the device current then
-  std::mutex mu;
-  Tables<double> owned;
   uint64_t *tw = nullptr;
 };
 
@@ -3110,30 +3104,6 @@ int check_ntt_size(long long n) {
   if (n < (1LL << kNttMinLog2N) || n > (1LL << kNttMaxLog2N))
     return fail(PDSP_ERR_UNSUPPORTED_SIZE, "NTT size %lld is outside %lld ... %lld", n, 1LL << kNttMinLog2N,
                 1LL << kNttMaxLog2N);
-  return PDSP_OK;
-}
-
-// The handle's device and table for one call on stream s
-int ntt_table(pdsp_ntt *h, hipStream_t s, const uint64_t **tw) {
-  if (int rc = require_device()) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (h->device < 0) PDSP_HIP_TRY(hipGetDevice(&h->device));
-  int count = 0;
-  PDSP_HIP_TRY(hipGetDeviceCount(&count));
-  if (h->device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", h->device, count);
-  if (!h->tw) {
-    if (int rc = refuse_upload_in_capture(s, "root table")) return rc;
-    DeviceGuard dg(h->device);
-    PDSP_HIP_TRY(dg.err);
-    std::vector<uint64_t> w((size_t)h->n / 2);
-    const uint64_t root = pdsp::gl::root(h->log2n);
-    uint64_t p = 1;
-    for (auto &v : w) v = p, p = pdsp::gl::mul(p, root);
-    if (hipError_t e = upload_table(h->owned, w, &h->tw))
-      return fail(PDSP_ERR_DEVICE, "HIP error %d (%s) at hipMalloc / hipMemcpy of the root table", (int)e,
-                  hipGetErrorString(e));
-  }
-  *tw = h->tw;
   return PDSP_OK;
 }
 
@@ -3157,26 +3127,31 @@ int ntt_t(const pdsp_ntt *ch, int op, long long batch, const uint64_t *a, long l
                 out_stride);
   }
   long long ac = 0, bc = 0, oc = 0;
-  if (batch > 0 && (!mad_ok(batch - 1, a_stride, a_len, &ac) || !mad_ok(batch - 1, out_stride, out_len, &oc) ||
-                    (conv && !mad_ok(batch - 1, b_stride, b_len, &bc)) || ac > (LLONG_MAX / 8) || bc > (LLONG_MAX / 8) ||
-                    oc > (LLONG_MAX / 8)))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  if (int rc = row_extents(batch, {{a_stride, a_len, &ac}, {out_stride, out_len, &oc},
+                                   {conv ? b_stride : 0, conv ? b_len : 0, &bc}}))
+    return rc;
   if (batch == 0) return PDSP_OK;
   if (!a || !out || (conv && !b)) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   if (int rc = check_grid(ntt_blocks(h->log2n, op, batch), batch)) return rc;
   // a thread stores the positions it loaded from `a`, after its last load: out == a at equal strides is exact in place.
   // Any other shared byte lets one thread's store reach another's load.
-  const bool in_place = (const void *)out == (const void *)a && a_stride == out_stride;
-  if ((!in_place && host_ranges_overlap(a, (size_t)ac * 8, out, (size_t)oc * 8)) ||
+  if ((!exact_in_place(out, out_stride, a, a_stride) && host_ranges_overlap(a, (size_t)ac * 8, out, (size_t)oc * 8)) ||
       (conv && host_ranges_overlap(b, (size_t)bc * 8, out, (size_t)oc * 8)))
     return fail(PDSP_ERR_BAD_ARG, conv ? "output overlaps an input (only out == a with equal strides may share bytes)"
                                        : "output overlaps input (only out == in with equal strides may share bytes)");
-  const uint64_t *tw = nullptr;
-  if (int rc = ntt_table(h, s, &tw)) return rc;
+  if (int rc = require_device()) return rc;
+  const int rc = first_use_table(*h, h->tw, s, "root table", [&] {  // omega_N^j, j < N / 2
+    std::vector<uint64_t> w((size_t)h->n / 2);
+    const uint64_t root = pdsp::gl::root(h->log2n);
+    uint64_t p = 1;
+    for (auto &v : w) v = p, p = pdsp::gl::mul(p, root);
+    return w;
+  });
+  if (rc) return rc;
   DeviceGuard dg(h->device);
   PDSP_HIP_TRY(dg.err);
-  return ntt_dev(h->log2n, op, batch, a, a_stride, (int)a_len, b, b_stride, (int)b_len, out, out_stride, (int)out_len, tw,
-                 s);
+  return ntt_dev(h->log2n, op, batch, a, a_stride, (int)a_len, b, b_stride, (int)b_len, out, out_stride, (int)out_len,
+                 h->tw, s);
 }
 
 int ntt_mul_t(long long count, const uint64_t *a, const uint64_t *b, uint64_t *out, hipStream_t s) {
@@ -3195,19 +3170,17 @@ int ntt_mul_t(long long count, const uint64_t *a, const uint64_t *b, uint64_t *o
 // device); the transform's own object lives for the call.  Buffer (8-byte values): out | a | b.
 int ntt_host(int op, const uint64_t *a, long long a_len, const uint64_t *b, long long b_len, bool b_shared,
              long long batch, long long n, uint64_t *out, long long out_len) {
-  struct Owner {
-    pdsp_ntt *p = nullptr;
-    ~Owner() { pdsp_ntt_destroy(p); }
-  } own;
-  if (int rc = pdsp_ntt_create(n, -1, &own.p)) return rc;
+  pdsp_ntt *h = nullptr;
+  if (int rc = pdsp_ntt_create(n, -1, &h)) return rc;
+  const HandleOwner<pdsp_ntt> own(h);
   const bool conv = op == 2;
   if (batch < 0) return fail(PDSP_ERR_BAD_ARG, "batch must be >= 0, got %lld", batch);
   if (conv && (a_len < 1 || a_len > n || b_len < 1 || b_len > n || out_len < 1 || out_len > n))
     return fail(PDSP_ERR_BAD_ARG, "lengths must be 1 ... N = %lld, got %lld (a), %lld (b) and %lld (out)", n, a_len, b_len,
                 out_len);
   long long na = 0, nb = 0, no = 0;
-  if (!mad_ok(batch, a_len, 0, &na) || !mad_ok(b_shared ? (batch > 0) : batch, b_len, 0, &nb) ||
-      !mad_ok(batch, out_len, 0, &no) || na > (1LL << 40) || nb > (1LL << 40) || no > (1LL << 40))
+  if (!host_count_ok(batch, a_len, &na) || !host_count_ok(b_shared ? (batch > 0) : batch, b_len, &nb) ||
+      !host_count_ok(batch, out_len, &no))
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x length overflows", batch);
   if (batch == 0) return PDSP_OK;
   if (!a || !out || (conv && !b)) return fail(PDSP_ERR_BAD_ARG, "null buffer");
@@ -3218,7 +3191,7 @@ int ntt_host(int op, const uint64_t *a, long long a_len, const uint64_t *b, long
         uint64_t *const d_out = (uint64_t *)d, *const d_a = d_out + no, *const d_b = d_a + na;
         PDSP_HIP_TRY(hipMemcpyAsync(d_a, a, (size_t)na * 8, hipMemcpyHostToDevice, s));
         if (conv) PDSP_HIP_TRY(hipMemcpyAsync(d_b, b, (size_t)nb * 8, hipMemcpyHostToDevice, s));
-        return ntt_t(own.p, op, batch, d_a, a_len, a_len, d_b, b_len, b_shared ? 0 : b_len, d_out, out_len, out_len, s);
+        return ntt_t(h, op, batch, d_a, a_len, a_len, d_b, b_len, b_shared ? 0 : b_len, d_out, out_len, out_len, s);
       },
       [&](const double *d) -> int {
         PDSP_HIP_TRY(hipMemcpy(out, d, (size_t)no * 8, hipMemcpyDeviceToHost));
@@ -3241,15 +3214,7 @@ int pdsp_ntt_create(long long n, int device, pdsp_ntt **out) {
   return PDSP_OK;
 }
 
-int pdsp_ntt_destroy(pdsp_ntt *h) {
-  if (!h) return PDSP_OK;
-  if (h->tw) {
-    DeviceGuard g(h->device);
-    h->owned.release();
-  }
-  delete h;
-  return PDSP_OK;
-}
+int pdsp_ntt_destroy(pdsp_ntt *h) { return destroy_handle(h); }
 
 long long pdsp_ntt_size(const pdsp_ntt *h) { return h ? h->n : 0; }
 
@@ -3292,18 +3257,20 @@ uint64_t pdsp_ntt_invmod(uint64_t a) { return pdsp::gl::inv(pdsp::gl::canon(a));
 // ---- sliding DFT: chosen bins at every hop ----------------------------------------------------------------------
 // A handle is its phase tables: per bin and component the N + 1 entries exp(-2 pi i (t1 +- t2)) of
 // include/pdsp_hip.h, evaluated in long double on the host from exactly reduced phases and rounded once per precision.
-// They go up at create time through the plans' uploader into the object's own lists.
+// They go up at create time through the plans' uploader into the handle's own lists (TableHandle).
 
-struct pdsp_sdft {
-  int device = -1;
+struct pdsp_sdft : TableHandle {
   long long n = 0, hop = 0;
   int nbins = 0, ncomp = 0, window = 0;
   std::vector<double> bins;
   double weights[5] = {0, 0, 0, 0, 0};
-  Tables<float> t32;  // owned: every allocation of this precision
-  Tables<double> t64;
   float2 *tab32 = nullptr;
   double2 *tab64 = nullptr;
+  template <typename T>
+  auto slot() const {
+    if constexpr (sizeof(T) == 4) return (const float2 *)tab32;
+    else return (const double2 *)tab64;
+  }
 };
 
 namespace pdsp_host {
@@ -3368,10 +3335,6 @@ long long sdft_frames(long long n, long long hop, long long samples) {
   return samples < n ? 0 : 1 + (samples - n) / hop;
 }
 
-template <typename T> const typename pdsp::vec2<T>::type *sdft_tab(const pdsp_sdft *c);
-template <> const float2 *sdft_tab<float>(const pdsp_sdft *c) { return c->tab32; }
-template <> const double2 *sdft_tab<double>(const pdsp_sdft *c) { return c->tab64; }
-
 template <typename T>
 int sdft_t(const pdsp_sdft *c, long long batch, const T *in, long long in_stride, long long samples, T *re_out,
            T *im_out, long long out_stride, hipStream_t s) {
@@ -3385,10 +3348,8 @@ int sdft_t(const pdsp_sdft *c, long long batch, const T *in, long long in_stride
     return fail(PDSP_ERR_BAD_ARG,
                 "strides must be >= %lld samples in and >= %lld frames out, got in_stride %lld, out_stride %lld", samples,
                 frames, in_stride, out_stride);
-  long long ic = 0, series = 0, oc = 0;
-  if (!mad_ok(batch - 1, in_stride, samples, &ic) || !mad_ok(batch, c->nbins, -1, &series) ||
-      !mad_ok(series, out_stride, frames, &oc) || ic > (LLONG_MAX / 8) || oc > (LLONG_MAX / 8))
-    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  long long ic = 0, oc = 0;  // a plane of the output holds one series of frames per bin and row
+  if (int rc = row_extents(batch, {{in_stride, samples, &ic}, {out_stride, frames, &oc, c->nbins}})) return rc;
   if (!in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   const long long blocks = sdft_blocks(c->n, sizeof(T), samples, c->nbins, batch);
   if (blocks < 0 || blocks > 0x7fffffffLL) return fail(PDSP_ERR_BAD_ARG, "batch too large: %lld", batch);
@@ -3401,7 +3362,7 @@ int sdft_t(const pdsp_sdft *c, long long batch, const T *in, long long in_stride
   DeviceGuard dg(c->device);
   PDSP_HIP_TRY(dg.err);
   return sdft_dev<T>(c->n, c->hop, c->nbins, c->ncomp, c->weights, batch, in, in_stride, samples, re_out, im_out,
-                     out_stride, sdft_tab<T>(c), s);
+                     out_stride, c->slot<T>(), s);
 }
 
 }  // namespace pdsp_host
@@ -3411,10 +3372,7 @@ int pdsp_sdft_create(long long window_len, long long nbins, const double *bins, 
   if (!out) return fail(PDSP_ERR_BAD_ARG, "out is null");
   if (int rc = check_sdft_args(window_len, nbins, bins, hop, window_type)) return rc;
   if (int rc = require_device()) return rc;
-  int count = 0;
-  PDSP_HIP_TRY(hipGetDeviceCount(&count));
-  if (device < 0) PDSP_HIP_TRY(hipGetDevice(&device));
-  if (device >= count) return fail(PDSP_ERR_BAD_ARG, "device %d out of range (%d visible)", device, count);
+  if (int rc = resolve_device(&device)) return rc;
   DeviceGuard g(device);
   PDSP_HIP_TRY(g.err);
   pdsp_sdft *c = new (std::nothrow) pdsp_sdft();
@@ -3445,16 +3403,7 @@ int pdsp_sdft_create(long long window_len, long long nbins, const double *bins, 
   return PDSP_OK;
 }
 
-int pdsp_sdft_destroy(pdsp_sdft *c) {
-  if (!c) return PDSP_OK;
-  {
-    DeviceGuard g(c->device);
-    c->t32.release();
-    c->t64.release();
-  }
-  delete c;
-  return PDSP_OK;
-}
+int pdsp_sdft_destroy(pdsp_sdft *c) { return destroy_handle(c); }
 
 long long pdsp_sdft_length(const pdsp_sdft *c) { return c ? c->n : 0; }
 long long pdsp_sdft_bins(const pdsp_sdft *c) { return c ? c->nbins : 0; }
@@ -3506,22 +3455,21 @@ int pdsp_sdft_host_f64(const double *in, long long batch, long long samples, lon
                 window_len);
   const long long frames = sdft_frames(window_len, hop, samples);
   long long cin = 0, series = 0, cout = 0;
-  if (!mad_ok(batch, samples, 0, &cin) || !mad_ok(batch, nbins, 0, &series) || !mad_ok(series, frames, 0, &cout) ||
-      cin > (1LL << 40) || cout > (1LL << 40))
+  if (!host_count_ok(batch, samples, &cin) || !host_count_ok(batch, nbins, &series) ||
+      !host_count_ok(series, frames, &cout))
     return fail(PDSP_ERR_BAD_ARG, "batch %lld x (%lld, %lld) overflows", batch, samples, frames);
   if (!in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   const size_t nx = (size_t)cin, ny = (size_t)cout;
-  struct Owner {
-    pdsp_sdft *p = nullptr;
-    ~Owner() { pdsp_sdft_destroy(p); }
-  } own;
+  HandleOwner<pdsp_sdft> own;
   return packed_host_call(
       64, PDSP_WIN_RECT, 2 * ny + nx,
       [&](pdsp_plan *plan, hipStream_t s, const double *, double *d) -> int {
-        if (int rc = pdsp_sdft_create(window_len, nbins, bins, hop, window_type, plan->device, &own.p)) return rc;
+        pdsp_sdft *c = nullptr;
+        if (int rc = pdsp_sdft_create(window_len, nbins, bins, hop, window_type, plan->device, &c)) return rc;
+        own.reset(c);
         double *const x = d + 2 * ny;
         PDSP_HIP_TRY(hipMemcpyAsync(x, in, nx * sizeof(double), hipMemcpyHostToDevice, s));
-        return sdft_t<double>(own.p, batch, x, samples, samples, d, d + ny, frames, s);
+        return sdft_t<double>(c, batch, x, samples, samples, d, d + ny, frames, s);
       },
       [&](const double *d) -> int {
         PDSP_HIP_TRY(hipMemcpy(re_out, d, ny * sizeof(double), hipMemcpyDeviceToHost));

@@ -167,3 +167,12 @@ def test_device_errors(pd):
     f = pd.FirFilter(np.ones(3), "cuda:0", torch.float32, block=64)
     with pytest.raises(pd.PdspError, match="unknown FIR mode"):
         f.apply(torch.ones(10, device="cuda:0"), "circular")
+    # a strided extent beyond LLONG_MAX / 8 elements has no byte size: refused before anything is launched (the extent
+    # itself, 2^61 + 10, still computes -- the overlap check used to multiply it by the element size and wrap)
+    lib, p = _capi.lib, lambda t: t.data_ptr()
+    x, y = torch.ones(20, device="cuda:0"), torch.zeros(20, device="cuda:0")
+    for x_stride, y_stride in ((1 << 61, 10), (10, 1 << 61)):
+        rc = lib.pdsp_fir_filter_f32(f.plan._h, 2, p(x), 10, x_stride, p(f.h_re), p(f.h_im), 3, 0, 10, p(y), y_stride, None)
+        assert rc == _capi.ERR_BAD_ARG and lib.pdsp_last_error().decode() == "batch 2 x stride overflows"
+    torch.cuda.synchronize()
+    assert float(y.abs().max()) == 0.0

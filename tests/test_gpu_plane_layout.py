@@ -117,3 +117,21 @@ def test_c_abi_planes_alloc_layout_and_parity(oracle_mod, scalar_bytes, tol):
         assert lib.pdsp_planes_alloc(None, rows, 4, 0, *[C.byref(p) for p in ptrs], C.byref(arena), None) == _capi.ERR_BAD_ARG
     finally:
         lib.pdsp_plan_destroy(plan)
+
+
+@pytest.mark.parametrize("scalar_bytes", [4, 8])
+def test_c_abi_planes_alloc_refuses_a_batch_no_launch_could_take(scalar_bytes):
+    """2^60 rows of 64 values: batch * n * scalar_bytes wraps a size_t (to 0 for f64).  The batch is refused as every
+    other entry point refuses it, before the product is formed; nothing is allocated and every output is null."""
+    import ctypes as C
+    from pragma_dsp_amd import _capi
+    lib, vp = _capi.lib, C.c_void_p
+    plan = vp()
+    _capi.check(lib.pdsp_plan_create(64, -1, C.byref(plan)))
+    try:
+        ptrs, arena, nbytes = [vp(1) for _ in range(4)], vp(1), C.c_ulonglong(1)
+        rc = lib.pdsp_planes_alloc(plan, 1 << 60, scalar_bytes, 0, *[C.byref(p) for p in ptrs], C.byref(arena), C.byref(nbytes))
+        assert rc == _capi.ERR_BAD_ARG and lib.pdsp_last_error().decode() == f"batch too large: {1 << 60}"
+        assert [p.value for p in ptrs] == [None] * 4 and arena.value is None and nbytes.value == 0
+    finally:
+        lib.pdsp_plan_destroy(plan)
