@@ -174,6 +174,25 @@ PDSP_API int pdsp_planes_free(pdsp_arena *arena);
 
 /* ---- device-pointer batched transforms (f32) --------------------------- */
 
+/* Aliasing, for every transform of this section and its f64 twin (DESIGN.md 4.1d has the reasoning
+ * kernel by kernel).  Planes are compared as byte ranges of batch * N scalars.
+ *   Single-pass sizes (N <= 16384 in f32, N <= 8192 in f64, and f64 real rows of N = 16384 at every
+ *   batch): an output plane may share bytes with an input plane only where the two begin at the same
+ *   address.  That admits the exact in-place call (re_out == re_in, im_out == im_in), the exchanged
+ *   one (re_out == im_in, im_out == re_in), either output plane alone on either input plane, and for
+ *   real rows re_out == re_in or im_out == re_in.  Each workgroup loads its rows whole before it
+ *   stores them, but no workgroup waits for another: an output that starts one element, one row or
+ *   half a plane into an input would race, and is refused.
+ *   Larger sizes run in several passes through planes of their own: any overlap of an output with an
+ *   input is accepted and correct.
+ *   At every size re_out and im_out must not overlap each other.
+ *   Interleaved rows: out == in is the one overlap allowed.
+ * Anything else is refused with PDSP_ERR_BAD_ARG before anything is launched -- "output overlaps
+ * input (an output plane may share bytes with an input plane only where the two begin at the same
+ * address)", "output overlaps input (only out == in may share bytes)" or "the output planes overlap
+ * each other" -- and pdsp_dev_transform_path_* (pdsp_hip_dev.h) refuses the same calls with the same
+ * text.  Buffers that touch without overlapping are legal. */
+
 /* Radix2Fft.forward(input) row by row, src/core/fft.ts:77-79: real input,
  * imaginary part taken as zero.  re_in[batch*N] -> re_out, im_out[batch*N]. */
 PDSP_API int pdsp_fft_forward_real_f32(const pdsp_plan *plan, long long batch,
@@ -190,7 +209,8 @@ PDSP_API int pdsp_fft_forward_complex_f32(const pdsp_plan *plan, long long batch
 /* The same forwardComplex / inverse on INTERLEAVED rows: in/out hold batch*N (re, im) pairs
  * (2*N scalars per row) -- the layout of I/Q streams and complex64 tensors.  An extension: the
  * reference's ComplexArray is planar (src/core/fft.ts:1-4).  Single-pass sizes only (N <= 16384
- * in f32, 8192 in f64; PDSP_ERR_UNSUPPORTED_SIZE beyond); out may alias in row for row. */
+ * in f32, 8192 in f64; PDSP_ERR_UNSUPPORTED_SIZE beyond); out == in runs in place, any other overlap
+ * of out with in is refused (see "Aliasing" above). */
 PDSP_API int pdsp_fft_forward_interleaved_f32(const pdsp_plan *plan, long long batch, const float *in,
                                               float *out, pdsp_stream stream);
 PDSP_API int pdsp_fft_inverse_interleaved_f32(const pdsp_plan *plan, long long batch, const float *in,
@@ -262,7 +282,13 @@ PDSP_API int pdsp_complex_op_f32(int op, long long count, const float *a_re, con
  *   window      N device floats, or NULL for "rect".
  *   amp_out     [batch][bins], bins = N/2+1 (one-sided) or N (two-sided).
  *   phase_out   same shape, or NULL.
- *   peak_out    [batch] int32 peak bin per frame, or NULL. */
+ *   peak_out    [batch] int32 peak bin per frame, or NULL.
+ * Aliasing (pdsp_spectrum_f32 / _f64 and pdsp_spectrum_peaks_f32, at every size): there is no
+ * in-place form.  amp_out, phase_out and peak_out / peaks_out share no byte with the frames' extent
+ * -- (batch-1)*frame_stride + min(frame_len, N) samples --, with the window's N values or with each
+ * other; a call that does is refused with PDSP_ERR_BAD_ARG, "output overlaps input (the spectrum has
+ * no in-place form)" or "the outputs overlap each other", before anything is launched, and by
+ * pdsp_dev_spectrum_path_* alike.  An output that begins right behind the last sample is legal. */
 PDSP_API int pdsp_spectrum_f32(const pdsp_plan *plan, long long batch,
                                const float *frames, long long frame_len, long long frame_stride,
                                const float *window, int sides,

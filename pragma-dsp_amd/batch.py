@@ -148,7 +148,12 @@ class BatchedFft(_device.Handle):
 
     # -- transforms ------------------------------------------------------------
     def forward(self, re: torch.Tensor, im: torch.Tensor | None = None, out=None):
-        """Rows of Radix2Fft.forward (im None) or .forwardComplex."""
+        """Rows of Radix2Fft.forward (im None) or .forwardComplex.  out = (out_re, out_im), or None for fresh planes.
+        Aliasing (include/pdsp_hip.h): up to the single-pass size (N <= 16384 in f32, 8192 in f64; f64 real rows also
+        16384) an output plane may share bytes with an input plane only where the two begin at the same address --
+        out=(re, im) runs in place, out=(im, re) and one plane of either are fine too, for real rows out_re or
+        out_im may be re -- and any other overlap raises PdspError(ERR_BAD_ARG, "output overlaps input ...") before
+        anything is launched; larger sizes take any overlap.  out_re and out_im never overlap each other."""
         batch, ore, oim = self._planes(re, im, out)
         s = _stream_ptr(self.device)
         if im is None:
@@ -159,6 +164,7 @@ class BatchedFft(_device.Handle):
         return ore, oim
 
     def inverse(self, re: torch.Tensor, im: torch.Tensor, out=None):
+        """Rows of Radix2Fft.inverse; `out` and its aliasing rule as forward()."""
         if im is None:
             raise PdspError(_capi.ERR_BAD_ARG, "the inverse needs both planes")
         batch, ore, oim = self._planes(re, im, out)
@@ -168,7 +174,8 @@ class BatchedFft(_device.Handle):
 
     def forward_interleaved(self, z: torch.Tensor, out: torch.Tensor | None = None, inverse: bool = False):
         """forwardComplex (or inverse) on rows of a complex64 / complex128 tensor [..., N] -- the
-        interleaved (re, im) layout of I/Q streams.  Single-pass sizes only."""
+        interleaved (re, im) layout of I/Q streams.  Single-pass sizes only.  out=z runs in place; an `out` that
+        overlaps z in any other way raises PdspError(ERR_BAD_ARG, "output overlaps input ...")."""
         operand(z, "input", self.device, COMPLEX[self.dtype], last=self.size)
         if out is None:
             out = torch.empty_like(z)
@@ -233,7 +240,9 @@ class BatchedFft(_device.Handle):
     def spectrum(self, frames: torch.Tensor, window="rect", sides: str = "one", want_phase: bool = False,
                  want_peak: bool = False, out=None):
         """Rows of spectrum()'s body: frames [..., L] (L <= N zero-padded, L > N
-        truncated: spectrum.ts:36-43) -> amplitude [..., bins] (+ phase, + peak bin)."""
+        truncated: spectrum.ts:36-43) -> amplitude [..., bins] (+ phase, + peak bin).  There is no in-place form:
+        an `out` that shares a byte with `frames` or with a window tensor raises PdspError(ERR_BAD_ARG, "output
+        overlaps input (the spectrum has no in-place form)") before anything is launched."""
         batch, length, shape = self._frames(frames)
         bins = self._bins(sides)
         # the amplitude rows are written through a raw pointer: exactly [..., bins], contiguous, on the plan's device

@@ -625,17 +625,6 @@ HostCut spectrum_cut(const pdsp_plan *plan, long long batch, long long bins) {
   return c;
 }
 
-inline bool host_ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
-// a*b + c without overflow into *out
-inline bool mad_ok(long long a, long long b, long long c, long long *out) {
-  long long p;
-  return !__builtin_mul_overflow(a, b, &p) && !__builtin_add_overflow(p, c, out);
-}
-
 // One strided operand of a row call: rows of `len` elements, `stride` elements apart, `per_batch` of them for each row
 // of the call (the sliding DFT's series: one per bin).  *count receives its extent in elements, from the first element
 // of the first row to the last of the last: (rows - 1) * stride + len.
@@ -659,10 +648,6 @@ int row_extents(long long batch, std::initializer_list<RowExtent> operands) {
 // The host forms' twin: batch contiguous rows of len values, at most 2^40 of them (the caller words the refusal).
 inline bool host_count_ok(long long batch, long long len, long long *count) {
   return mad_ok(batch, len, 0, count) && *count <= (1LL << 40);
-}
-// The one overlap of an output with its input that the row kernels with an in-place form allow: the same rows.
-inline bool exact_in_place(const void *out, long long out_stride, const void *in, long long in_stride) {
-  return out == in && out_stride == in_stride;
 }
 
 // The element-wise kernels read index i of every input before they write index i and touch no other index, so an

@@ -1,5 +1,6 @@
 // pdsp_dispatch.inc -- kernel dispatch by size and call shape (templates on the scalar type T), included by the
 // kernel translation units (pdsp_kernels_*.hip), which instantiate it explicitly; see pdsp_internal.h.
+#include <climits>
 #include <cstdint>
 #include <cstring>
 #include <type_traits>
@@ -62,9 +63,7 @@ void place_peak_rows(const void *peaks, T *&amp, T *&ph, T *at, size_t rows) {
 // their first scratch pair only when this is false.
 template <typename T>
 bool planes_overlap(const T *re_in, const T *im_in, const T *re_out, const T *im_out, size_t plane_bytes) {
-  auto hit = [&](const T *a, const T *b) {
-    return a && b && (const char *)a < (const char *)b + plane_bytes && (const char *)b < (const char *)a + plane_bytes;
-  };
+  auto hit = [&](const T *a, const T *b) { return host_ranges_overlap(a, plane_bytes, b, plane_bytes); };
   return hit(re_in, re_out) || hit(re_in, im_out) || hit(im_in, re_out) || hit(im_in, im_out);
 }
 
@@ -687,14 +686,35 @@ Intermediates<T> intermediates(const Pick &p, T *sc, size_t plane, T *re_out, T 
 }
 
 // The argument checks of run_complex, shared with transform_path (batch == 0 passes: nothing to do)
+// Aliasing (DESIGN.md 4.1d has the reasoning kernel by kernel).  Every single-pass kernel gives a workgroup the same
+// rows on its input and output sides and loads them whole before its first store, but no workgroup waits for
+// another: an output plane may share bytes with an input plane only where the two begin at the same address -- in
+// place, exchanged (re_out == im_in, im_out == re_in) or one plane of either.  Shifted by an element, a row or half
+// a plane, one workgroup's stores race another's loads.  The multi-pass sizes read the input in a first pass of its
+// own (pick_transform draws the scratch for that) and take any overlap.  A size is single-pass by the plan and the
+// call's kind alone, never by alignment, batch or a switch: f64 real rows of N = 16384 count as single-pass at every
+// batch, because fft_real_kernel runs them from 8 rows on.  Output planes that overlap each other race at every size.
 template <typename T>
-int check_transform(const pdsp_plan *plan, long long batch, const T *re_in, const T *re_out, const T *im_out) {
+int check_transform(const pdsp_plan *plan, long long batch, const T *re_in, const T *im_in, const T *re_out,
+                    const T *im_out) {
   if (int rc = check_plan_batch(plan, batch)) return rc;
   if (batch == 0) return PDSP_OK;
   if (!re_in || !re_out || !im_out) return fail(PDSP_ERR_BAD_ARG, "null buffer");
-  if (!tables<T>(plan).tw)
+  const Tables<T> &t = tables<T>(plan);
+  if (!t.tw)
     return fail(PDSP_ERR_UNSUPPORTED_SIZE, "FFT size %lld exceeds the %d-bit limit %d", plan->n, (int)(8 * sizeof(T)),
                 pdsp_max_size((int)sizeof(T)));
+  const size_t bytes = (size_t)batch * (size_t)plan->n * sizeof(T);
+  if (t.log2n1 <= 0 || (sizeof(T) == 8 && !im_in && plan->log2n == 14)) {
+    auto clash = [&](const T *out, const T *in) {  // the disjoint call leaves at the first comparison
+      return host_ranges_overlap(out, bytes, in, bytes) && !exact_in_place(out, plan->n, in, plan->n);
+    };
+    if (clash(re_out, re_in) || clash(im_out, re_in) || clash(re_out, im_in) || clash(im_out, im_in))
+      return fail(PDSP_ERR_BAD_ARG, "output overlaps input (an output plane may share bytes with an input plane only "
+                                    "where the two begin at the same address)");
+  }
+  if (host_ranges_overlap(re_out, bytes, im_out, bytes))
+    return fail(PDSP_ERR_BAD_ARG, "the output planes overlap each other");
   return PDSP_OK;
 }
 
@@ -702,7 +722,7 @@ int check_transform(const pdsp_plan *plan, long long batch, const T *re_in, cons
 template <typename T>
 int transform_path(const pdsp_plan *plan, long long batch, const T *re_in, const T *im_in, const T *re_out,
                    const T *im_out, int *info) {
-  if (int rc = check_transform<T>(plan, batch, re_in, re_out, im_out)) return rc;
+  if (int rc = check_transform<T>(plan, batch, re_in, im_in, re_out, im_out)) return rc;
   if (!info) return fail(PDSP_ERR_BAD_ARG, "null buffer");
   const Pick p = batch ? pick_transform<T>(plan, batch, re_in, im_in, re_out, im_out) : Pick{};
   std::memcpy(info, &p, sizeof(p));
@@ -712,7 +732,7 @@ int transform_path(const pdsp_plan *plan, long long batch, const T *re_in, const
 template <typename T>
 int run_complex(const pdsp_plan *plan, long long batch, const T *re_in, const T *im_in, T *re_out, T *im_out, T scale,
                 hipStream_t s, bool by_size) {
-  if (int rc = check_transform<T>(plan, batch, re_in, re_out, im_out)) return rc;
+  if (int rc = check_transform<T>(plan, batch, re_in, im_in, re_out, im_out)) return rc;
   if (batch == 0) return PDSP_OK;
   const Pick p = pick_transform<T>(plan, batch, re_in, im_in, re_out, im_out, by_size);
   const Tables<T> &t = tables<T>(plan);
@@ -812,6 +832,11 @@ int run_interleaved(const pdsp_plan *plan, long long batch, const T *in, T *out,
   if (!t.tw || t.log2n1 > 0)
     return fail(PDSP_ERR_UNSUPPORTED_SIZE, "interleaved rows are single-pass only: FFT size %lld exceeds %d", plan->n,
                 1 << max_log2n<T>());
+  // fft_stockham_kernel loads a workgroup's rows whole before it stores them and waits for no other workgroup: the
+  // same rows, or no byte in common
+  if (const size_t bytes = (size_t)batch * (size_t)plan->n * 2 * sizeof(T);
+      host_ranges_overlap(out, bytes, in, bytes) && !exact_in_place(out, plan->n, in, plan->n))
+    return fail(PDSP_ERR_BAD_ARG, "output overlaps input (only out == in may share bytes)");
   DeviceGuard g(plan->device);
   PDSP_HIP_TRY(g.err);
   const pdsp::cx<T> *zin = reinterpret_cast<const pdsp::cx<T> *>(in);
@@ -844,7 +869,7 @@ int launch_complex_op(long long count, const float *are, const float *aim, const
 // The argument checks of spectrum_impl, shared with spectrum_path (batch == 0 passes: nothing to do)
 template <typename T>
 int check_spectrum(const pdsp_plan *plan, long long batch, const T *frames, long long frame_len, long long frame_stride,
-                   int sides, const T *amp_out, const T *phase_out, const int32_t *peak_idx_out,
+                   const T *window, int sides, const T *amp_out, const T *phase_out, const int32_t *peak_idx_out,
                    const pdsp_peak32 *peaks_out, double sample_rate) {
   if (int rc = check_plan_batch(plan, batch)) return rc;
   if (sides != PDSP_SIDES_ONE && sides != PDSP_SIDES_TWO) return fail(PDSP_ERR_BAD_ARG, "bad sides %d", sides);
@@ -862,6 +887,23 @@ int check_spectrum(const pdsp_plan *plan, long long batch, const T *frames, long
   // a frame with samples on the complex kernel of (x, 0): N < 64, the sizes without packed-real tables
   if (frame_len > 0 && !t.tw_half && t.log2n1 <= 0 && (!t.tw || plan->log2n > 5))
     return fail(PDSP_ERR_UNSUPPORTED_SIZE, "no spectrum tables for size %lld", plan->n);
+  // Aliasing: a frame's samples become bins of another length in another order, frames may overlap each other
+  // (frame_stride < frame_len), and the peak kernels read the amplitude and phase rows back: no output shares a byte
+  // with the frames' extent, with the window's N values or with another output, at any size (DESIGN.md 4.1d).
+  const long long n = plan->n, bins = sides == PDSP_SIDES_ONE ? n / 2 + 1 : n, used = frame_len < n ? frame_len : n;
+  long long in_count = 0;
+  if (used > 0 && (!mad_ok(batch - 1, frame_stride, used, &in_count) || in_count > (LLONG_MAX / 8)))
+    return fail(PDSP_ERR_BAD_ARG, "batch %lld x stride overflows", batch);
+  const size_t ib = (size_t)in_count * sizeof(T), wb = (size_t)n * sizeof(T), rb = (size_t)batch * (size_t)bins * sizeof(T);
+  const void *const out[4] = {amp_out, phase_out, peak_idx_out, peaks_out};
+  const size_t ob[4] = {rb, rb, (size_t)batch * sizeof(int32_t), (size_t)batch * sizeof(pdsp_peak32)};
+  for (int i = 0; i < 4; ++i) {
+    if (host_ranges_overlap(out[i], ob[i], frames, ib) || host_ranges_overlap(out[i], ob[i], window, wb))
+      return fail(PDSP_ERR_BAD_ARG, "output overlaps input (the spectrum has no in-place form)");
+    for (int j = 0; j < i; ++j)
+      if (host_ranges_overlap(out[i], ob[i], out[j], ob[j]))
+        return fail(PDSP_ERR_BAD_ARG, "the outputs overlap each other");
+  }
   return PDSP_OK;
 }
 
@@ -870,7 +912,7 @@ template <typename T>
 int spectrum_path(const pdsp_plan *plan, long long batch, const T *frames, long long frame_len, long long frame_stride,
                   const T *window, int sides, const T *amp_out, const T *phase_out, const int32_t *peak_idx_out,
                   const pdsp_peak32 *peaks_out, double sample_rate, int *info) {
-  if (int rc = check_spectrum<T>(plan, batch, frames, frame_len, frame_stride, sides, amp_out, phase_out, peak_idx_out,
+  if (int rc = check_spectrum<T>(plan, batch, frames, frame_len, frame_stride, window, sides, amp_out, phase_out, peak_idx_out,
                                  peaks_out, sample_rate))
     return rc;
   if (!info) return fail(PDSP_ERR_BAD_ARG, "null buffer");
@@ -885,7 +927,7 @@ template <typename T>
 int spectrum_impl(const pdsp_plan *plan, long long batch, const T *frames, long long frame_len, long long frame_stride,
                   const T *window, int sides, T *amp_out, T *phase_out, int32_t *peak_idx_out, pdsp_peak32 *peaks_out,
                   double sample_rate, hipStream_t stream) {
-  if (int rc = check_spectrum<T>(plan, batch, frames, frame_len, frame_stride, sides, amp_out, phase_out, peak_idx_out,
+  if (int rc = check_spectrum<T>(plan, batch, frames, frame_len, frame_stride, window, sides, amp_out, phase_out, peak_idx_out,
                                  peaks_out, sample_rate))
     return rc;
   if (batch == 0) return PDSP_OK;

@@ -258,6 +258,24 @@ inline int check_plan_batch(const pdsp_plan *plan, long long batch) {
   return check_grid(batch, batch);  // one workgroup per row at most; far beyond any HBM-resident batch
 }
 
+// Byte ranges, not pointer equality: do [a, a + a_bytes) and [b, b + b_bytes) share a byte?  A null pointer or an empty
+// range shares none.  (pdsp_capi.hip's argument checks and pdsp_dispatch.inc's.)
+inline bool host_ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// a*b + c without overflow into *out
+inline bool mad_ok(long long a, long long b, long long c, long long *out) {
+  long long p;
+  return !__builtin_mul_overflow(a, b, &p) && !__builtin_add_overflow(p, c, out);
+}
+
+// The one overlap of an output with its input that the row kernels with an in-place form allow: the same rows.
+inline bool exact_in_place(const void *out, long long out_stride, const void *in, long long in_stride) {
+  return out == in && out_stride == in_stride;
+}
+
 // ---- kernel dispatchers: defined in pdsp_dispatch.inc, instantiated for float / double in the kernel units -------
 // Rows of planar complex points -> rows (forward; the callers swap planes and pass 1/N for the inverse).
 // by_size: the kernel variant is chosen from the plan and the call's kind alone, never from `batch` (the host forms,
