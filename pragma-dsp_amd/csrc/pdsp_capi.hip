@@ -425,7 +425,7 @@ hipError_t upload_multipass_tables(Tables<T> &t, int log2n, long long size) {
 template <typename T>
 hipError_t upload_packed_tables(Tables<T> &t, int log2n, long long size) {
   using T2 = typename pdsp::vec2<T>::type;
-  if (hipError_t e = upload_table(t, build_twiddles<T2>(log2n - 1, pdsp::packed_log2e(log2n - 1)), &t.tw_half)) return e;
+  if (hipError_t e = upload_table(t, build_twiddles<T2>(log2n - 1), &t.tw_half)) return e;
   std::vector<T2> twr, tw4;
   add_cos_sin(twr, (size_t)(size / 4 + 1), [&](size_t k) { return (-2.0 * M_PI * (double)k) / (double)size; });
   if (hipError_t e = upload_table(t, twr, &t.twr)) return e;
@@ -2529,7 +2529,7 @@ int chirp_create(H **out, const char *what, int device, long long length, long l
   h->device = device, h->length = length, h->bins = bins, h->log2m = chirp_log2m(length, bins), h->m = 1LL << h->log2m;
   auto upload = [&](auto &t, auto &s) -> hipError_t {
     using T2 = std::remove_pointer_t<decltype(s.pre)>;
-    if (hipError_t e = upload_table(t, build_twiddles<T2>(h->log2m, pdsp::packed_log2e(h->log2m)), &s.tw)) return e;
+    if (hipError_t e = upload_table(t, build_twiddles<T2>(h->log2m), &s.tw)) return e;
     if (hipError_t e = upload_table(t, chirp_round<T2>(pre), &s.pre)) return e;
     if (!post) s.post = s.pre;
     else if (hipError_t e = upload_table(t, chirp_round<T2>(*post), &s.post)) return e;

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "pdsp_internal.h"
+#include "pdsp_fft_kernel.h"
 
 namespace pdsp_host {
 
@@ -389,7 +390,7 @@ hipError_t launch_packed_one(bool fast, const T *frames, const T *win, int wmode
                              long long stride, const typename pdsp::vec2<T>::type *tw,
                              const typename pdsp::vec2<T>::type *twr, T *amp, T *ph, int two_sided, T s_edge, T s_mid,
                              pdsp::PeakRec *peaks, T freq_scale, long long batch, hipStream_t s) {
-  using TR = pdsp::FftTraits<LOG2M, pdsp::packed_log2e(LOG2M)>;
+  using TR = pdsp::FftTraits<LOG2M>;
   const long long ngroups = (batch + TR::ROWS - 1) / TR::ROWS;
   const dim3 block(TR::WG);
   auto launch = [&](auto fast_c, auto win_c) {

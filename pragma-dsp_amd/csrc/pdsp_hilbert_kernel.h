@@ -31,7 +31,7 @@ template <int V>
 using int_k = std::integral_constant<int, V>;
 
 // ENVELOPE, |a + i h|.
-// f64 is range-safe, as mag(cx<double>) is (pdsp_fft_kernel.h), because the host forms restate
+// f64 is range-safe, as mag(cx<double>) is (pdsp_fft_core.h), because the host forms restate
 // np.abs(scipy.signal.hilbert(x)), a hypot: sqrt(a^2 + h^2) in f64 is Inf above |a| = 1.3e154 and 0 below 1.5e-162.  Both
 // operands are scaled by 2^-e, e the exponent of the larger one (frexp: that one lands in [0.5, 1)), the squares are
 // summed there, and the root is scaled back: three ldexp and one frexp_exp on top of the plain form, every one of them

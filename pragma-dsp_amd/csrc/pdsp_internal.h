@@ -33,7 +33,7 @@
 
 #include "../../include/pdsp_hip.h"
 #include "../../include/pdsp_hip_dev.h"
-#include "pdsp_fft_kernel.h"
+#include "pdsp_fft_core.h"
 
 namespace pdsp_host {
 
@@ -242,7 +242,7 @@ R with_int(int v, R outside, const F &f) {
 // threads) for `rows` rows; the packed sizes are 5 <= log2m <= 13 (N = 64 ... 16384)
 template <int LOG2M>
 dim3 packed_grid(long long rows) {
-  constexpr int R = pdsp::FftTraits<LOG2M, pdsp::packed_log2e(LOG2M)>::ROWS;
+  constexpr int R = pdsp::FftTraits<LOG2M>::ROWS;
   return dim3((unsigned)((rows + R - 1) / R));
 }
 

@@ -1,5 +1,5 @@
 // pdsp_ntt_kernel.h -- the number-theoretic transform over GF(2^64 - 2^32 + 1) (pdsp_goldilocks.h) and the exact cyclic
-// convolution built on it, in the shape of the Stockham rows of pdsp_fft_kernel.h: one row of N = 2^LOG2N points per
+// convolution built on it, in the shape of the Stockham rows of pdsp_fft_rows_kernel.h: one row of N = 2^LOG2N points per
 // TP = N / E threads, E points in registers, an autosort exchange through one LDS row between passes.
 //
 // A pass of radix R on Ns-point sub-transforms (Ns the product of the radices before it) takes, for j < N / R,

@@ -15,7 +15,7 @@
 // the 2 of the split and the 1/M of the inverse make the 1/N.
 #pragma once
 
-#include "pdsp_fft_kernel.h"
+#include "pdsp_fft_core.h"
 
 namespace pdsp {
 
@@ -23,10 +23,12 @@ namespace pdsp {
 // __shared__ cx<T> lds[PackedRow<T, LOG2M>::TR::LDS_ELEMS], and passes the number of rows of the launch.
 template <typename T, int LOG2M>
 struct PackedRow {
-  static constexpr int LOG2E = packed_log2e(LOG2M);
+  // sixteen points per thread, so that W_N^(TP q) = W_32^q.  (Eight at LOG2M = 13 -- half the registers, 8 waves per
+  // SIMD, one more LDS pass -- measured 6 % slower on the spectrum kernel, tools/kbench; that option is gone.)
+  static constexpr int LOG2E = 4;
   using TR = FftTraits<LOG2M, LOG2E>;
   static constexpr int E = TR::E, TP = TR::TP, M = TR::N;
-  static_assert(LOG2M >= 5 && LOG2E == 4, "packed path: TP >= 2, sixteen points per thread (W_N^(TP q) = W_32^q)");
+  static_assert(LOG2M >= 5, "packed path: TP >= 2");
 
   int tid;
   bool live;
@@ -66,6 +68,20 @@ struct PackedRow {
   __device__ __forceinline__ Split forward_split(const int k, const int k2) const {
     return Split{lrow[lds_pad(k)], lrow[lds_pad(k2)]};
   }
+  // The same for k = tid + TP q, at constant offsets from three bases made once behind the passes when TP % 16 == 0
+  // (k, k2 then only name the pair): Z[k] at pad(tid) + cpad(TP q), Z[M-k] at pad(M - tid) - cpad(TP q), Z[M] == Z[0].
+  // The six later families keep forward_split(k, k2): moving them changes their instruction streams; out of scope here.
+  struct Pairs {
+    const cx<T> *lrow, *zlo, *zhi, *zhi0;
+    template <int q>
+    __device__ __forceinline__ Split forward_split(std::integral_constant<int, q>, const int k, const int k2) const {
+      if constexpr (TP % 16 == 0) return Split{zlo[cpad(TP * q)], q == 0 ? zhi0[0] : *(zhi - cpad(TP * q))};
+      else return Split{lrow[lds_pad(k)], lrow[lds_pad(k2)]};
+    }
+  };
+  __device__ __forceinline__ Pairs pairs(const cx<T> *const lrow) const {  // lrow: this row, as the kernel spells it
+    return Pairs{lrow, lrow + lds_pad(tid), lrow + lds_pad(M - tid), lrow + lds_pad((M - tid) & (M - 1))};
+  }
 
   // conj(2 Z_y[k]) and conj(2 Z_y[M-k]) into the row's LDS from ya = Y[k], yb = Y[M-k]; k2 = M - k, or that mod M
   // (read only when k != 0); w = W_N^k
@@ -86,17 +102,18 @@ struct PackedRow {
   }
 };
 
-// The twiddles of a packed-real row: the M-point transform's (twf: per-thread register bases when TP >= 16, else
-// the table) and the split's, W_N^tid.  Where each kernel loads them is its own choice (load_order_fence's header).
-template <typename T, int LOG2M>
+// The twiddles of a packed-real row: the M-point transform's (twf: per-thread register bases when REG, by default
+// when TP >= 16, else the table; spectrum_staged_kernel keeps register bases below that, its bits depend on it) and
+// the split's, W_N^tid.  Where each kernel loads them is its own choice (load_order_fence's header).
+template <typename T, int LOG2M, bool REG = (PackedRow<T, LOG2M>::TP >= 16)>
 struct PackedTwiddles {
   using PR = PackedRow<T, LOG2M>;
   using V2 = typename vec2<T>::type;
-  std::conditional_t<(PR::TP >= 16), RegTwiddles<T, LOG2M, PR::LOG2E>, TableTwiddles<T, LOG2M, PR::LOG2E>> twf;
+  std::conditional_t<REG, RegTwiddles<T, LOG2M, PR::LOG2E>, TableTwiddles<T, LOG2M, PR::LOG2E>> twf;
   cx<T> twk0;
 
   __device__ __forceinline__ void load_passes(const V2 *tw, const int tid) {
-    if constexpr (PR::TP >= 16) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
+    if constexpr (REG) twf.load(reinterpret_cast<const cx<T> *>(tw), tid);
     else twf.tw = reinterpret_cast<const cx<T> *>(tw);
   }
   __device__ __forceinline__ void load_split(const V2 *twr, const int tid) {

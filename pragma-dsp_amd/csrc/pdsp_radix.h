@@ -32,7 +32,7 @@ struct RadixPlan {
 };
 
 // log2e: points per thread (4 = sixteen, the default; 3 = eight: half the registers, twice the
-// waves, one more LDS pass -- what the VALU-issue-bound packed-real kernel at M = 8192 wants).
+// waves, one more LDS pass).
 constexpr RadixPlan make_radix_plan(int log2n, int log2e = 4) {
   RadixPlan p{};
   p.log2n = log2n;
@@ -63,11 +63,5 @@ constexpr RadixPlan make_radix_plan(int log2n, int log2e = 4) {
   p.twcount = off;
   return p;
 }
-
-// Points per thread of the packed-real spectrum kernel, by log2 of its N/2-point transform.
-#ifndef PDSP_PACKED_LOG2E_13
-#define PDSP_PACKED_LOG2E_13 4  /* 3 (eight points per thread, 8 waves/SIMD) measured 6 % slower: tools/kbench */
-#endif
-constexpr int packed_log2e(int log2m) { return log2m == 13 ? PDSP_PACKED_LOG2E_13 : 4; }
 
 }  // namespace pdsp

@@ -38,7 +38,7 @@
 // it is a frame.
 #pragma once
 
-#include "pdsp_fft_kernel.h"
+#include "pdsp_fft_core.h"
 
 #pragma clang fp contract(off)
 

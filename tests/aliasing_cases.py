@@ -31,7 +31,7 @@ PLANAR = ("complex", "real", "inverse")
 
 
 def rows_per_workgroup(kernel, n):
-    """Rows of N points one workgroup of `kernel` holds (pdsp_fft_kernel.h: FftTraits, the 4096-point chunks of the
+    """Rows of N points one workgroup of `kernel` holds (pdsp_fft_core.h: FftTraits, the 4096-point chunks of the
     staged kernels, the packed-real rows of N / 2 points)."""
     if kernel in ("fft_tiny_staged_kernel", "fft_staged_kernel", "fft_tiny_staged_kernel<AMP>"):
         return 4096 // n

@@ -1,4 +1,4 @@
-"""The stand-alone element-wise kernels of pdsp_fft_kernel.h (apply_window_kernel, polar_kernel, complex_op_kernel),
+"""The stand-alone element-wise kernels of pdsp_elementwise_kernel.h (apply_window_kernel, polar_kernel, complex_op_kernel),
 their launchers and their entry points, path by path against numpy f64 references computed from the same inputs
 rounded to the dtype.
 

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 
 def packed_rows_per_wg(n):
-    """FftTraits<log2(n/2), packed_log2e>::ROWS of the packed-real kernels on N-point rows (one thread per 32 samples)."""
+    """FftTraits<log2(n/2)>::ROWS of the packed-real kernels on N-point rows (one thread per 32 samples)."""
     tp = n // 32
     return max(tp, 256) // tp
 

@@ -86,14 +86,14 @@ static int spec_main(long long frames, int rounds) {
     CK(hipMemcpy(win, w.data(), n * 4, hipMemcpyHostToDevice));
   }
   std::vector<float2> tw, twr(n / 4 + 1);
-  fill_tw(13, tw, pdsp::packed_log2e(13));
+  fill_tw(13, tw);
   for (int k = 0; k <= n / 4; ++k) twr[k] = make_float2((float)cos(-2 * M_PI * k / n), (float)sin(-2 * M_PI * k / n));
   float2 *dtw, *dtwr;
   CK(hipMalloc(&dtw, tw.size() * 8));
   CK(hipMemcpy(dtw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
   CK(hipMalloc(&dtwr, twr.size() * 8));
   CK(hipMemcpy(dtwr, twr.data(), twr.size() * 8, hipMemcpyHostToDevice));
-  using TR = pdsp::FftTraits<13, pdsp::packed_log2e(13)>;
+  using TR = pdsp::FftTraits<13>;
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
