@@ -4,13 +4,7 @@
 //   X[k] = sum_n x[n] a^-n w^(n k),  w = exp(-2 pi i step),  a = radius exp(2 pi i start),  L + m - 1 <= 8192,
 // with step and start in TURNS (the tables' phases are formed exactly from these doubles).  There is no inverse.
 const native = require('./native');
-
-// plain arrays or typed arrays only: nothing else reaches the addon
-function toF64(a, name) {
-  if (a instanceof Float64Array) return a;
-  if (Array.isArray(a) || (ArrayBuffer.isView(a) && !(a instanceof DataView))) return Float64Array.from(a);
-  throw new TypeError(name + ' must be an array or a typed array');
-}
+const { toF64 } = require('./_util');
 
 function num(v, name, dflt) {
   if (v === undefined || v === null) return dflt;

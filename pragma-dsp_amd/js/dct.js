@@ -4,25 +4,17 @@
 // (include/pdsp_hip.h, "discrete cosine transform").  Conventions are scipy dct / idct's; norm 'backward'
 // (default), 'ortho' or 'forward'.  The signal length is a power of two, 64 ... 16384.
 const native = require('./native');
+const { dflt, lookup, toF64 } = require('./_util');
 
 const NORMS = { backward: 0, ortho: 1, forward: 2 };
 const SWAP = { backward: 'forward', ortho: 'ortho', forward: 'backward' };
 
-// plain arrays or typed arrays only: nothing else reaches the addon
-function toF64(a, name) {
-  if (a instanceof Float64Array) return a;
-  if (Array.isArray(a) || (ArrayBuffer.isView(a) && !(a instanceof DataView))) return Float64Array.from(a);
-  throw new TypeError(name + ' must be an array or a typed array');
-}
-
 function options(opts) {
   const o = opts || {};
-  const type = o.type === undefined || o.type === null ? 2 : o.type;
-  const norm = o.norm === undefined || o.norm === null ? 'backward' : o.norm;
+  const type = dflt(o.type, 2);
+  const norm = dflt(o.norm, 'backward');
   if (type !== 2 && type !== 3) throw new Error('DCT type must be 2 or 3, got ' + type);
-  if (!Object.prototype.hasOwnProperty.call(NORMS, norm)) {
-    throw new Error("DCT norm must be 'backward', 'ortho' or 'forward', got " + norm);
-  }
+  lookup(NORMS, norm, "DCT norm must be 'backward', 'ortho' or 'forward', got " + norm);
   return { type, norm };
 }
 

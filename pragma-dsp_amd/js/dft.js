@@ -3,13 +3,7 @@
 // computed on the device in f64 by Bluestein's chirp-z algorithm (include/pdsp_hip.h, "any-length DFT").  Conventions
 // are numpy's fft / ifft: X[k] = sum_n x[n] exp(-2 pi i n k / L), no scaling forward, 1 / L on the inverse.
 const native = require('./native');
-
-// plain arrays or typed arrays only: nothing else reaches the addon
-function toF64(a, name) {
-  if (a instanceof Float64Array) return a;
-  if (Array.isArray(a) || (ArrayBuffer.isView(a) && !(a instanceof DataView))) return Float64Array.from(a);
-  throw new TypeError(name + ' must be an array or a typed array');
-}
+const { toF64 } = require('./_util');
 
 function run(inverse, real, imag) {
   const re = toF64(real, 'real');

@@ -2,8 +2,8 @@
 // Drop-in for `pragma-dsp/xform/fourier` (reference src/xform/fourier.ts).
 const native = require('./native');
 const core = require('./core');
+const { WINDOW_IDS, windowId } = require('./_util');
 
-const WINDOW_IDS = { rect: 0, hann: 1, hamming: 2, blackman: 3 };
 const toF64 = core._toF64;
 
 // fourier.ts:14-52 -- host f64 (an f32 window would miss the 1e-8 golden tolerance)
@@ -12,11 +12,9 @@ function createWindow(type, size) {
     throw new Error('Window size must be positive, got ' + size);
   }
   if (size === 1) return new Float64Array([1]);
-  if (!Object.prototype.hasOwnProperty.call(WINDOW_IDS, type)) {
-    throw new Error('Unsupported window type: ' + type);
-  }
+  const id = windowId(type);
   const out = new Float64Array(size);
-  native.windowMake(WINDOW_IDS[type], size, out);
+  native.windowMake(id, size, out);
   return out;
 }
 

@@ -4,19 +4,13 @@
 // (include/pdsp_hip.h, "Hilbert transform").  Conventions are scipy.signal.hilbert(signal, N = n)'s: the signal is
 // zero-padded to n, a power of two, 64 ... 16384 (default: the signal's own length), and every result has n values.
 const native = require('./native');
+const { dflt, toF64 } = require('./_util');
 
 const MODES = { analytic: 0, imag: 1, envelope: 2, phase: 3 };
 
-// plain arrays or typed arrays only: nothing else reaches the addon
-function toF64(a, name) {
-  if (a instanceof Float64Array) return a;
-  if (Array.isArray(a) || (ArrayBuffer.isView(a) && !(a instanceof DataView))) return Float64Array.from(a);
-  throw new TypeError(name + ' must be an array or a typed array');
-}
-
 function size(x, opts) {
   const o = opts || {};
-  const n = o.n === undefined || o.n === null ? x.length : o.n;
+  const n = dflt(o.n, x.length);
   if (typeof n !== 'number' || !Number.isInteger(n)) throw new Error('n must be an integer, got ' + n);
   return n;
 }

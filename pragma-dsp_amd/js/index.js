@@ -47,54 +47,31 @@ module.exports = {
     binFrequencies: fourier.binFrequencies,
   },
 };
-// pragma-dsp/filters: a module the reference only plans (ROADMAP.md, "Filters and utilities").  Reachable as
-// `.filters` but not enumerated, so that the key list of the reference's three surfaces stays exactly theirs.
-Object.defineProperty(module.exports, 'filters', {
-  value: {
+// The modules below are ones the reference only plans (ROADMAP.md) or extensions beside it.  Each is reachable under
+// its name but not enumerated, so that the key list of the reference's three surfaces stays exactly theirs.
+const hidden = [
+  // pragma-dsp/filters (ROADMAP.md, "Filters and utilities")
+  ['filters', {
     firFilter: filters.firFilter,
     resamplePoly: resample.resamplePoly,
     upfirdn: resample.upfirdn,
     designResampleTaps: resample.designResampleTaps,
-  },
-  enumerable: false,
-});
-// pragma-dsp/xform/stft: planned by the reference (ROADMAP.md, "A) STFT"), not enumerated for the same reason.
-Object.defineProperty(module.exports, 'stft', {
-  value: { stft: stft.stft, istft: stft.istft },
-  enumerable: false,
-});
-// pragma-dsp/xform/dct: planned by the reference (ROADMAP.md, v0.3), not enumerated for the same reason.
-Object.defineProperty(module.exports, 'dct', {
-  value: { dct: dct.dct, idct: dct.idct },
-  enumerable: false,
-});
-// Hilbert / analytic signal helpers: planned by the reference (ROADMAP.md, v0.3), not enumerated for the same reason.
-Object.defineProperty(module.exports, 'hilbert', {
-  value: { hilbert: hilbert.hilbert, envelope: hilbert.envelope, instantaneousPhase: hilbert.instantaneousPhase },
-  enumerable: false,
-});
-// Any-length DFT: an extension beside the reference's power-of-two Radix2Fft, not enumerated for the same reason.
-Object.defineProperty(module.exports, 'dft', {
-  value: { dft: dft.dft, idft: dft.idft },
-  enumerable: false,
-});
-// Wavelets: planned by the reference (ROADMAP.md, item E), not enumerated for the same reason.
-Object.defineProperty(module.exports, 'wavelet', {
-  value: { wavedec: wavelet.wavedec, waverec: wavelet.waverec, waveletTaps: wavelet.waveletTaps },
-  enumerable: false,
-});
-// Chirp-z transform and zoom FFT: an extension beside the any-length DFT, not enumerated for the same reason.
-Object.defineProperty(module.exports, 'czt', {
-  value: { czt: czt.czt, zoomFft: czt.zoomFft },
-  enumerable: false,
-});
-// Number-theoretic transform: planned by the reference (ROADMAP.md, item F), not enumerated for the same reason.
-Object.defineProperty(module.exports, 'ntt', {
-  value: { ntt: ntt.ntt, intt: ntt.intt, polymul: ntt.polymul, MODULUS: ntt.MODULUS },
-  enumerable: false,
-});
-// Sliding DFT: planned by the reference (ROADMAP.md, item B), not enumerated for the same reason.
-Object.defineProperty(module.exports, 'sdft', {
-  value: { slidingDft: sdft.slidingDft, goertzel: sdft.goertzel },
-  enumerable: false,
-});
+  }],
+  // pragma-dsp/xform/stft (ROADMAP.md, "A) STFT")
+  ['stft', { stft: stft.stft, istft: stft.istft }],
+  // pragma-dsp/xform/dct (ROADMAP.md, v0.3)
+  ['dct', { dct: dct.dct, idct: dct.idct }],
+  // Hilbert / analytic signal helpers (ROADMAP.md, v0.3)
+  ['hilbert', { hilbert: hilbert.hilbert, envelope: hilbert.envelope, instantaneousPhase: hilbert.instantaneousPhase }],
+  // any-length DFT: an extension beside the reference's power-of-two Radix2Fft
+  ['dft', { dft: dft.dft, idft: dft.idft }],
+  // wavelets (ROADMAP.md, item E)
+  ['wavelet', { wavedec: wavelet.wavedec, waverec: wavelet.waverec, waveletTaps: wavelet.waveletTaps }],
+  // chirp-z transform and zoom FFT: an extension beside the any-length DFT
+  ['czt', { czt: czt.czt, zoomFft: czt.zoomFft }],
+  // number-theoretic transform (ROADMAP.md, item F)
+  ['ntt', { ntt: ntt.ntt, intt: ntt.intt, polymul: ntt.polymul, MODULUS: ntt.MODULUS }],
+  // sliding DFT (ROADMAP.md, item B)
+  ['sdft', { slidingDft: sdft.slidingDft, goertzel: sdft.goertzel }],
+];
+for (const [name, value] of hidden) Object.defineProperty(module.exports, name, { value, enumerable: false });

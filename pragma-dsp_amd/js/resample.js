@@ -3,10 +3,7 @@
 // uniform grid", "windowed-sinc filter design helpers"; no implementation there yet).  The root export lists these
 // under `.filters`, beside firFilter (index.js).
 const native = require('./native');
-
-function toF64(a) {
-  return a instanceof Float64Array ? a : Float64Array.from(a);
-}
+const { looseF64 } = require('./_util');
 
 // Polyphase rate change in f64 (include/pdsp_hip.h, "polyphase rate change"): scipy.signal.resample_poly's and
 // scipy.signal.upfirdn's definitions, one time-domain launch on the device per call.
@@ -29,13 +26,14 @@ function designResampleTaps(up, down) {
 // "constant": ceil(len up / down) outputs.
 function resamplePoly(signal, up, down, taps) {
   ratio(up, down);
-  const h = taps === undefined || taps === null ? new Float64Array(0) : toF64(taps);
-  if (taps !== undefined && taps !== null && h.length < 1) {
+  const given = taps !== undefined && taps !== null;
+  const h = given ? looseF64(taps) : new Float64Array(0);
+  if (given && h.length < 1) {
     throw new Error('filter must have at least one tap, got 0');
   }
   const n = up >= 1 && down >= 1 && up <= 8192 && down <= 8192 ? Math.ceil((signal.length * up) / down) : 0;
   const out = new Float64Array(n);
-  native.resamplePoly(toF64(signal), up, down, h, out);
+  native.resamplePoly(looseF64(signal), up, down, h, out);
   return out;
 }
 
@@ -47,7 +45,7 @@ function upfirdn(h, signal, up, down) {
   ratio(up, down);
   const ok = up >= 1 && down >= 1 && up <= 8192 && down <= 8192 && signal.length >= 1 && h.length >= 1 && h.length <= 8192;
   const out = new Float64Array(ok ? Math.floor(((signal.length - 1) * up + h.length - 1) / down) + 1 : 0);
-  native.upfirdn(toF64(h), toF64(signal), up, down, out);
+  native.upfirdn(looseF64(h), looseF64(signal), up, down, out);
   return out;
 }
 

@@ -4,22 +4,13 @@
 // Frame m is signal[m*hop, m*hop + size); bin b of it is Y = sum_n w[n] x[n] e^{-2 pi i b n / size}, unscaled, with b
 // in cycles per window: fractional, negative and >= size all allowed.  2 <= size <= 16384 (any integer), 1 ... 256 bins.
 const native = require('./native');
-
-const WINDOWS = { rect: 0, hann: 1, hamming: 2, blackman: 3 };
-
-// plain arrays or typed arrays only: nothing else reaches the addon
-function toF64(a, name) {
-  if (a instanceof Float64Array) return a;
-  if (Array.isArray(a) || (ArrayBuffer.isView(a) && !(a instanceof DataView))) return Float64Array.from(a);
-  throw new TypeError(name + ' must be an array or a typed array');
-}
+const { dflt, toF64, windowId } = require('./_util');
 
 // slidingDft(signal, size, bins, hop = 1, window = 'rect') -> { frames, bins, real, imag }, real / imag row-major
 // [bins][frames] Float64Arrays (time fastest), frames = 1 + floor((signal.length - size) / hop).
 function slidingDft(signal, size, bins, hop, window) {
-  const h = hop === undefined || hop === null ? 1 : hop;
-  const w = window === undefined || window === null ? 'rect' : window;
-  if (!Object.prototype.hasOwnProperty.call(WINDOWS, w)) throw new Error('Unsupported window type: ' + w);
+  const h = dflt(hop, 1);
+  const w = windowId(dflt(window, 'rect'));
   if (!Number.isInteger(size)) throw new Error('size must be an integer, got ' + size);
   if (!Number.isInteger(h)) throw new Error('hop must be an integer, got ' + h);
   const x = toF64(signal, 'signal');
@@ -28,7 +19,7 @@ function slidingDft(signal, size, bins, hop, window) {
   const ok = size >= 2 && size <= 16384 && h >= 1 && x.length >= size && b.length >= 1 && b.length <= 256;
   const frames = ok ? 1 + Math.floor((x.length - size) / h) : 0;
   const real = new Float64Array(frames * b.length), imag = new Float64Array(frames * b.length);
-  native.sdft(x, size, b, h, WINDOWS[w], real, imag);
+  native.sdft(x, size, b, h, w, real, imag);
   return { frames, bins: b.length, real, imag };
 }
 

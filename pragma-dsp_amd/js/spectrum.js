@@ -5,21 +5,20 @@
 const native = require('./native');
 const core = require('./core');
 const fourier = require('./fourier');
+const { dflt, lookup } = require('./_util');
 
 function spectrum(samples, options) {
   const opts = options || {};
-  const sampleRate = opts.sampleRate === undefined || opts.sampleRate === null ? 1 : opts.sampleRate;
-  const sides = opts.sides === undefined || opts.sides === null ? 'one' : opts.sides;
+  const sampleRate = dflt(opts.sampleRate, 1);
+  const sides = dflt(opts.sides, 'one');
   const targetSize = opts.fftSize === undefined || opts.fftSize === null
     ? core.nextPowerOfTwo(samples.length) : opts.fftSize;
-  const windowType = opts.window === undefined || opts.window === null ? 'rect' : opts.window;
+  const windowType = dflt(opts.window, 'rect');
   // error order of spectrum.ts:114-132: FFT ctor, createWindow, binFrequencies
   if (!core.isPowerOfTwo(targetSize)) {
     throw new Error('FFT size must be power of two, got ' + targetSize);
   }
-  if (targetSize !== 1 && !Object.prototype.hasOwnProperty.call(fourier._WINDOW_IDS, windowType)) {
-    throw new Error('Unsupported window type: ' + windowType);
-  }
+  if (targetSize !== 1) lookup(fourier._WINDOW_IDS, windowType, 'Unsupported window type: ' + windowType);
   if (sampleRate <= 0) {
     throw new Error('Sample rate must be positive, got ' + sampleRate);
   }
@@ -40,9 +39,9 @@ function spectrum(samples, options) {
 // amplitude and phase of a run are views into one buffer each, frequencies is a fresh copy per result.
 function spectrumBatch(frames, options) {
   const opts = options || {};
-  const sampleRate = opts.sampleRate === undefined || opts.sampleRate === null ? 1 : opts.sampleRate;
-  const sides = opts.sides === undefined || opts.sides === null ? 'one' : opts.sides;
-  const windowType = opts.window === undefined || opts.window === null ? 'rect' : opts.window;
+  const sampleRate = dflt(opts.sampleRate, 1);
+  const sides = dflt(opts.sides, 'one');
+  const windowType = dflt(opts.window, 'rect');
   const one = sides === 'one';
   const id = fourier._WINDOW_IDS[windowType];
   const out = [];
@@ -55,9 +54,7 @@ function spectrumBatch(frames, options) {
     const targetSize = opts.fftSize === undefined || opts.fftSize === null ? core.nextPowerOfTwo(len) : opts.fftSize;
     // error order of spectrum.ts:114-132: FFT ctor, createWindow, binFrequencies
     if (!core.isPowerOfTwo(targetSize)) throw new Error('FFT size must be power of two, got ' + targetSize);
-    if (targetSize !== 1 && !Object.prototype.hasOwnProperty.call(fourier._WINDOW_IDS, windowType)) {
-      throw new Error('Unsupported window type: ' + windowType);
-    }
+    if (targetSize !== 1) lookup(fourier._WINDOW_IDS, windowType, 'Unsupported window type: ' + windowType);
     if (sampleRate <= 0) throw new Error('Sample rate must be positive, got ' + sampleRate);
     const bins = one ? Math.floor(targetSize / 2) + 1 : targetSize;
     const frequencies = new Float64Array(bins);
@@ -100,7 +97,7 @@ function spectrumBatch(frames, options) {
 // Map<"type:size", window> of FourierLive, index.ts:30-48) -- so a result is yielded at most batchFrames frames
 // after its input was drawn.  Each frame is copied when it is drawn (a producer may refill one buffer per frame).
 function* spectrumStream(frames, options, batchFrames) {
-  const limit = batchFrames === undefined || batchFrames === null ? 256 : batchFrames;
+  const limit = dflt(batchFrames, 256);
   if (!(limit >= 1)) throw new Error('batchFrames must be >= 1, got ' + limit);
   let pending = [];
   for (const f of frames) {

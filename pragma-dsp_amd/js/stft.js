@@ -4,26 +4,17 @@
 // "short-time transform").  Frame b is signal[b*hopSize, b*hopSize + fftSize); its bins are unscaled,
 // X[k] = sum_n w[n] x[n] e^{-2 pi i k n / N}, k = 0 ... N/2.  64 <= fftSize <= 16384.
 const native = require('./native');
-
-const WINDOWS = { rect: 0, hann: 1, hamming: 2, blackman: 3 };
-
-// plain arrays or typed arrays only: nothing else reaches the addon
-function toF64(a, name) {
-  if (a instanceof Float64Array) return a;
-  if (Array.isArray(a) || (ArrayBuffer.isView(a) && !(a instanceof DataView))) return Float64Array.from(a);
-  throw new TypeError(name + ' must be an array or a typed array');
-}
+const { dflt, toF64, windowId } = require('./_util');
 
 function options(opts) {
   const o = opts || {};
-  const window = o.window === undefined || o.window === null ? 'hann' : o.window;
-  if (!Object.prototype.hasOwnProperty.call(WINDOWS, window)) throw new Error('Unsupported window type: ' + window);
+  const window = windowId(dflt(o.window, 'hann'));
   const fftSize = o.fftSize, hopSize = o.hopSize;
   if (!Number.isInteger(fftSize)) throw new Error('fftSize must be an integer, got ' + fftSize);
   if (!Number.isInteger(hopSize)) throw new Error('hopSize must be an integer, got ' + hopSize);
   // sizes the library refuses go to it with empty outputs: it fails before touching them, with its own message
   const ok = fftSize >= 64 && fftSize <= 16384 && hopSize >= 1;
-  return { fftSize, hopSize, window: WINDOWS[window], ok };
+  return { fftSize, hopSize, window, ok };
 }
 
 // stft(signal, { fftSize, hopSize, window = 'hann' }) -> { frames, bins, real, imag }, real / imag row-major

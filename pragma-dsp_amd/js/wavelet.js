@@ -7,13 +7,7 @@
 // and the inverse is its transpose.  `wavelet` is 'haar', 'db1' ... 'db10', or an array of taps (even length 2 ... 32,
 // orthonormal to 1e-10); the signal's length must be a multiple of 2^levels.
 const native = require('./native');
-
-// plain arrays or typed arrays only: nothing else reaches the addon
-function toF64(a, name) {
-  if (a instanceof Float64Array) return a;
-  if (Array.isArray(a) || (ArrayBuffer.isView(a) && !(a instanceof DataView))) return Float64Array.from(a);
-  throw new TypeError(name + ' must be an array or a typed array');
-}
+const { toF64 } = require('./_util');
 
 function run(mode, signal, wavelet, levels) {
   const x = toF64(signal, 'signal');

@@ -3,23 +3,13 @@
 // {op, signal, type, norm, typed}; typed = 'f32' hands the signal in as Float32Array, 'f64' as Float64Array, else a
 // plain array; type / norm null are left out of the options.  Writes the values (or {error}) in order, then the
 // root's Object.keys as the last entry.
-const fs = require('fs');
-const path = require('path');
-const p = require(path.join(__dirname, '..', '..', 'pragma-dsp_amd', 'js'));
+const { p, conv, runCases } = require('./_cases');
 
-const conv = (a, typed) => (typed === 'f32' ? Float32Array.from(a) : typed === 'f64' ? Float64Array.from(a) : a);
-const cases = JSON.parse(fs.readFileSync(process.argv[2], 'utf8'));
-const out = cases.map((c) => {
-  try {
-    const opts = {};
-    if (c.type !== null) opts.type = c.type;
-    if (c.norm !== null) opts.norm = c.norm;
-    const y = p.dct[c.op](conv(c.signal, c.typed), opts);
-    if (!(y instanceof Float64Array)) return { error: 'not a Float64Array' };
-    return Array.from(y);
-  } catch (e) {
-    return { error: e.message };
-  }
-});
-out.push(Object.keys(p));
-fs.writeFileSync(process.argv[3], JSON.stringify(out));
+runCases((c) => {
+  const opts = {};
+  if (c.type !== null) opts.type = c.type;
+  if (c.norm !== null) opts.norm = c.norm;
+  const y = p.dct[c.op](conv(c.signal, c.typed), opts);
+  if (!(y instanceof Float64Array)) return { error: 'not a Float64Array' };
+  return Array.from(y);
+}, [Object.keys(p)]);

@@ -3,22 +3,12 @@
 // {op, real, imag, typed}; typed = 'f32' hands the planes in as Float32Array, 'f64' as Float64Array, else plain
 // arrays; imag null is left out of the call.  Writes {real, imag} or {error} in order, then the root's Object.keys as
 // the last entry.
-const fs = require('fs');
-const path = require('path');
-const p = require(path.join(__dirname, '..', '..', 'pragma-dsp_amd', 'js'));
+const { p, conv, runCases } = require('./_cases');
 
-const conv = (a, typed) => (typed === 'f32' ? Float32Array.from(a) : typed === 'f64' ? Float64Array.from(a) : a);
-const cases = JSON.parse(fs.readFileSync(process.argv[2], 'utf8'));
-const out = cases.map((c) => {
-  try {
-    const args = [conv(c.real, c.typed)];
-    if (c.imag !== null) args.push(conv(c.imag, c.typed));
-    const y = p.dft[c.op](...args);
-    if (!(y.real instanceof Float64Array) || !(y.imag instanceof Float64Array)) return { error: 'not Float64Arrays' };
-    return { real: Array.from(y.real), imag: Array.from(y.imag) };
-  } catch (e) {
-    return { error: e.message };
-  }
-});
-out.push(Object.keys(p));
-fs.writeFileSync(process.argv[3], JSON.stringify(out));
+runCases((c) => {
+  const args = [conv(c.real, c.typed)];
+  if (c.imag !== null) args.push(conv(c.imag, c.typed));
+  const y = p.dft[c.op](...args);
+  if (!(y.real instanceof Float64Array) || !(y.imag instanceof Float64Array)) return { error: 'not Float64Arrays' };
+  return { real: Array.from(y.real), imag: Array.from(y.imag) };
+}, [Object.keys(p)]);

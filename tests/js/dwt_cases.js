@@ -3,21 +3,11 @@
 // on each case {op, signal, wavelet, levels, typed}; typed = 'f32' hands the arrays in as Float32Array, 'f64' as
 // Float64Array, else plain arrays; a wavelet given as an array of taps is converted the same way.  Writes {values} or
 // {error} in order, then the root's Object.keys as the last entry.
-const fs = require('fs');
-const path = require('path');
-const p = require(path.join(__dirname, '..', '..', 'pragma-dsp_amd', 'js'));
+const { p, conv, runCases } = require('./_cases');
 
-const conv = (a, typed) => (typed === 'f32' ? Float32Array.from(a) : typed === 'f64' ? Float64Array.from(a) : a);
-const cases = JSON.parse(fs.readFileSync(process.argv[2], 'utf8'));
-const out = cases.map((c) => {
-  try {
-    const wv = Array.isArray(c.wavelet) ? conv(c.wavelet, c.typed === 'f32' ? 'f64' : c.typed) : c.wavelet;
-    const y = c.op === 'waveletTaps' ? p.wavelet.waveletTaps(c.wavelet) : p.wavelet[c.op](conv(c.signal, c.typed), wv, c.levels);
-    if (!(y instanceof Float64Array)) return { error: 'not a Float64Array' };
-    return { values: Array.from(y) };
-  } catch (e) {
-    return { error: e.message };
-  }
-});
-out.push(Object.keys(p));
-fs.writeFileSync(process.argv[3], JSON.stringify(out));
+runCases((c) => {
+  const wv = Array.isArray(c.wavelet) ? conv(c.wavelet, c.typed === 'f32' ? 'f64' : c.typed) : c.wavelet;
+  const y = c.op === 'waveletTaps' ? p.wavelet.waveletTaps(c.wavelet) : p.wavelet[c.op](conv(c.signal, c.typed), wv, c.levels);
+  if (!(y instanceof Float64Array)) return { error: 'not a Float64Array' };
+  return { values: Array.from(y) };
+}, [Object.keys(p)]);

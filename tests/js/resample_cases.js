@@ -3,28 +3,18 @@
 // (pragma-dsp_amd/js, `.filters`) on each case {op, signal, up, down, taps, typed}; typed = 'f32' hands the signal
 // in as Float32Array, 'f64' as Float64Array, else a plain array; taps null is left out; up / down null are left out
 // of upfirdn (its defaults).  Writes the values or {error} in order, then the root's Object.keys as the last entry.
-const fs = require('fs');
-const path = require('path');
-const p = require(path.join(__dirname, '..', '..', 'pragma-dsp_amd', 'js'));
+const { p, conv, runCases } = require('./_cases');
 
-const conv = (a, typed) => (typed === 'f32' ? Float32Array.from(a) : typed === 'f64' ? Float64Array.from(a) : a);
-const cases = JSON.parse(fs.readFileSync(process.argv[2], 'utf8'));
-const out = cases.map((c) => {
-  try {
-    let y;
-    if (c.op === 'designResampleTaps') y = p.filters.designResampleTaps(c.up, c.down);
-    else if (c.op === 'resamplePoly') {
-      y = c.taps === null ? p.filters.resamplePoly(conv(c.signal, c.typed), c.up, c.down)
-        : p.filters.resamplePoly(conv(c.signal, c.typed), c.up, c.down, c.taps);
-    } else {
-      y = c.up === null ? p.filters.upfirdn(c.taps, conv(c.signal, c.typed))
-        : p.filters.upfirdn(c.taps, conv(c.signal, c.typed), c.up, c.down);
-    }
-    if (!(y instanceof Float64Array)) return { error: 'not a Float64Array' };
-    return Array.from(y);
-  } catch (e) {
-    return { error: e.message };
+runCases((c) => {
+  let y;
+  if (c.op === 'designResampleTaps') y = p.filters.designResampleTaps(c.up, c.down);
+  else if (c.op === 'resamplePoly') {
+    y = c.taps === null ? p.filters.resamplePoly(conv(c.signal, c.typed), c.up, c.down)
+      : p.filters.resamplePoly(conv(c.signal, c.typed), c.up, c.down, c.taps);
+  } else {
+    y = c.up === null ? p.filters.upfirdn(c.taps, conv(c.signal, c.typed))
+      : p.filters.upfirdn(c.taps, conv(c.signal, c.typed), c.up, c.down);
   }
-});
-out.push(Object.keys(p));
-fs.writeFileSync(process.argv[3], JSON.stringify(out));
+  if (!(y instanceof Float64Array)) return { error: 'not a Float64Array' };
+  return Array.from(y);
+}, [Object.keys(p)]);

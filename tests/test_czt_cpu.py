@@ -339,7 +339,8 @@ def test_js_declarations_match_czt_exports():
     idx = open(os.path.join(JS, "index.d.ts")).read()
     assert re.search(r"export const czt: \{\s*czt: typeof cztNs\.czt;\s*zoomFft: typeof cztNs\.zoomFft;\s*\};", idx)
     js = open(os.path.join(JS, "index.js")).read()
-    assert re.search(r"defineProperty\(module\.exports, 'czt', \{\s*value: \{ czt: czt\.czt, zoomFft: czt\.zoomFft \},\s*"
-                     r"enumerable: false,", js)
+    assert re.search(r"\['czt', \{ czt: czt\.czt, zoomFft: czt\.zoomFft \}\],", js)   # a row of the table of non-enumerable sub-modules
+    assert re.search(r"for \(const \[name, value\] of hidden\) Object\.defineProperty\(module\.exports, name, \{ value, "
+                     r"enumerable: false \}\);", js)
     napi = open(os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.c")).read()
     assert napi.count("pdsp_czt_") == 1 and '{"czt", Czt}' in napi  # one binding, of the host form

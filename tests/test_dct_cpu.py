@@ -170,5 +170,6 @@ def test_js_declarations_match_dct_exports():
     idx = open(os.path.join(JS, "index.d.ts")).read()
     assert re.search(r"export const dct: \{\s*dct: typeof dctNs\.dct;\s*idct: typeof dctNs\.idct;\s*\};", idx)
     js = open(os.path.join(JS, "index.js")).read()
-    assert re.search(r"defineProperty\(module\.exports, 'dct', \{\s*value: \{ dct: dct\.dct, idct: dct\.idct \},\s*"
-                     r"enumerable: false,", js)
+    assert re.search(r"\['dct', \{ dct: dct\.dct, idct: dct\.idct \}\],", js)   # a row of the table of non-enumerable sub-modules
+    assert re.search(r"for \(const \[name, value\] of hidden\) Object\.defineProperty\(module\.exports, name, \{ value, "
+                     r"enumerable: false \}\);", js)

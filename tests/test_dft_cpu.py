@@ -145,7 +145,8 @@ def test_js_declarations_match_dft_exports():
     idx = open(os.path.join(JS, "index.d.ts")).read()
     assert re.search(r"export const dft: \{\s*dft: typeof dftNs\.dft;\s*idft: typeof dftNs\.idft;\s*\};", idx)
     js = open(os.path.join(JS, "index.js")).read()
-    assert re.search(r"defineProperty\(module\.exports, 'dft', \{\s*value: \{ dft: dft\.dft, idft: dft\.idft \},\s*"
-                     r"enumerable: false,", js)
+    assert re.search(r"\['dft', \{ dft: dft\.dft, idft: dft\.idft \}\],", js)   # a row of the table of non-enumerable sub-modules
+    assert re.search(r"for \(const \[name, value\] of hidden\) Object\.defineProperty\(module\.exports, name, \{ value, "
+                     r"enumerable: false \}\);", js)
     napi = open(os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.c")).read()
     assert napi.count("pdsp_dft_") == 1 and '{"dft", Dft}' in napi  # one binding, of the host form

@@ -2,31 +2,17 @@
 phases of test_czt_cpu (grid_direct: dyadic steps and starts) on seeded inputs at the f64 bound of test_gpu_czt: plain /
 Float64Array / Float32Array inputs, real and complex, the defaults, the error texts, and the root's key list, which
 `.czt` must not join."""
-import json
-import os
-import shutil
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
+import js_host
 from test_czt_cpu import GRID, grid_direct, row_err
 from test_gpu_czt import bound
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADDON = os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.node")
-NODE = shutil.which("node")
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(NODE is None or not os.path.exists(ADDON), reason="node or the addon is not available")]
-
-
-def run_cases(cases, tmp_path):
-    cin, cout = tmp_path / "cases.json", tmp_path / "out.json"
-    cin.write_text(json.dumps(cases))
-    subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "czt_cases.js"), str(cin), str(cout)], check=True,
-                   timeout=120)
-    res = json.loads(cout.read_text())
-    return res[:-1], res[-1]
+pytestmark = [pytest.mark.gpu, js_host.needs_node]
+run_cases = functools.partial(js_host.run_cases, "czt_cases.js")
 
 
 def test_js_czt_against_the_direct_sum(tmp_path):

@@ -1,31 +1,17 @@
 """dft / idft of the JS host (pragma-dsp_amd/js `.dft`, through the N-API addon) against numpy.fft.fft / ifft on seeded
 inputs at the f64 bound of test_gpu_dft: L = 3, 1000 and 4095, plain / Float64Array / Float32Array inputs, real and
 complex, the error texts, and the root's key list, which `.dft` must not join."""
-import json
-import os
-import shutil
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
+import js_host
 from test_dft_cpu import row_err
 from test_gpu_dft import bound
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADDON = os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.node")
-NODE = shutil.which("node")
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(NODE is None or not os.path.exists(ADDON), reason="node or the addon is not available")]
-
-
-def run_cases(cases, tmp_path):
-    cin, cout = tmp_path / "cases.json", tmp_path / "out.json"
-    cin.write_text(json.dumps(cases))
-    subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "dft_cases.js"), str(cin), str(cout)], check=True,
-                   timeout=120)
-    res = json.loads(cout.read_text())
-    return res[:-1], res[-1]
+pytestmark = [pytest.mark.gpu, js_host.needs_node]
+run_cases = functools.partial(js_host.run_cases, "dft_cases.js")
 
 
 def test_js_dft_against_numpy(tmp_path):

@@ -1,34 +1,20 @@
 """wavedec / waverec / waveletTaps of the JS host (pragma-dsp_amd/js `.wavelet`, through the N-API addon) against the
 numpy restatement of tests/test_dwt_cpu.py at the f64 bounds of test_gpu_dwt, on plain arrays, Float64Array and
 Float32Array; the error texts; and the root's key list, which `.wavelet` must not join."""
-import json
-import os
-import shutil
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+import js_host
 import pragma_dsp_amd as pd
 from test_dwt_cpu import band_levels, lattice_taps, wavedec_ref, waverec_ref
 from test_gpu_dwt import hold
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADDON = os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.node")
-NODE = shutil.which("node")
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(NODE is None or not os.path.exists(ADDON), reason="node or the addon is not available")]
+pytestmark = [pytest.mark.gpu, js_host.needs_node]
+run_cases = functools.partial(js_host.run_cases, "dwt_cases.js")
 EPS = 2.0 ** -52
-
-
-def run_cases(cases, tmp_path):
-    cin, cout = tmp_path / "cases.json", tmp_path / "out.json"
-    cin.write_text(json.dumps(cases))
-    subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "dwt_cases.js"), str(cin), str(cout)], check=True,
-                   timeout=120)
-    res = json.loads(cout.read_text())
-    return res[:-1], res[-1]
 
 
 def test_js_wavelet_against_the_restatement(tmp_path):

@@ -2,32 +2,18 @@
 against the f64 numpy restatement of test_hilbert_cpu on seeded inputs, at the f64 bound of test_gpu_hilbert: plain /
 Float64Array / Float32Array inputs, with and without padding, the error texts, and the root's key list, which
 `.hilbert` must not join."""
-import json
-import os
-import shutil
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
+import js_host
 from test_gpu_hilbert import bound, err_rows
 from test_hilbert_cpu import hilbert_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADDON = os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.node")
-NODE = shutil.which("node")
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(NODE is None or not os.path.exists(ADDON), reason="node or the addon is not available")]
+pytestmark = [pytest.mark.gpu, js_host.needs_node]
+run_cases = functools.partial(js_host.run_cases, "hilbert_cases.js")
 OPS = {"hilbert": "analytic", "envelope": "envelope", "instantaneousPhase": "phase"}
-
-
-def run_cases(cases, tmp_path):
-    cin, cout = tmp_path / "cases.json", tmp_path / "out.json"
-    cin.write_text(json.dumps(cases))
-    subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "hilbert_cases.js"), str(cin), str(cout)], check=True,
-                   timeout=120)
-    res = json.loads(cout.read_text())
-    return res[:-1], res[-1]
 
 
 def test_js_hilbert_against_numpy(tmp_path):

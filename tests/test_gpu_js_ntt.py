@@ -2,30 +2,16 @@
 reference of tests/ntt_ref.py, on BigUint64Array, BigInt64Array and arrays of BigInt, at the vectors of the host-form
 test of test_gpu_ntt (N = 64 and 4096); the error texts; and the root's key list, which `.ntt` must not join.  Equality
 of 64-bit integers, no tolerance."""
-import json
-import os
-import shutil
-import subprocess
+import functools
 
 import pytest
 
+import js_host
 import ntt_ref
 from ntt_ref import P
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADDON = os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.node")
-NODE = shutil.which("node")
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(NODE is None or not os.path.exists(ADDON), reason="node or the addon is not available")]
-
-
-def run_cases(cases, tmp_path):
-    cin, cout = tmp_path / "cases.json", tmp_path / "out.json"
-    cin.write_text(json.dumps(cases))
-    subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "ntt_cases.js"), str(cin), str(cout)], check=True,
-                   timeout=120)
-    res = json.loads(cout.read_text())
-    return res[:-2], res[-2], res[-1]
+pytestmark = [pytest.mark.gpu, js_host.needs_node]
+run_cases = functools.partial(js_host.run_cases, "ntt_cases.js", tail=2)
 
 
 def strs(v):

@@ -2,32 +2,18 @@
 against the f64 restatement of the definition in test_resample_cpu on seeded inputs, at the f64 bound of
 test_gpu_resample ((T + 2) 2^-52 A[m] per output): plain / Float64Array / Float32Array inputs, default and user taps,
 the error texts, and the root's key list, which `.filters` must not join."""
-import json
-import os
-import shutil
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
+import js_host
 import pragma_dsp_amd as pd
 from test_resample_cpu import poly_setup, resample_ref, user_taps
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADDON = os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.node")
-NODE = shutil.which("node")
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(NODE is None or not os.path.exists(ADDON), reason="node or the addon is not available")]
+pytestmark = [pytest.mark.gpu, js_host.needs_node]
+run_cases = functools.partial(js_host.run_cases, "resample_cases.js")
 EPS = 2.0 ** -52
-
-
-def run_cases(cases, tmp_path):
-    cin, cout = tmp_path / "cases.json", tmp_path / "out.json"
-    cin.write_text(json.dumps(cases))
-    subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "resample_cases.js"), str(cin), str(cout)], check=True,
-                   timeout=120)
-    res = json.loads(cout.read_text())
-    return res[:-1], res[-1]
 
 
 def held(got, x, up, down, h, t0, y_len):

@@ -1,25 +1,16 @@
 """stft / istft of the JS host (pragma-dsp_amd/js `.stft`, through the N-API addon) against numpy on seeded inputs:
 plain / Float64Array / Float32Array inputs, every window type, and the error texts."""
-import json
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADDON = os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.node")
-NODE = shutil.which("node")
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(NODE is None or not os.path.exists(ADDON), reason="node or the addon is not available")]
+import js_host
+
+pytestmark = [pytest.mark.gpu, js_host.needs_node]
 
 
 def run_cases(cases, tmp_path):
-    cin, cout = tmp_path / "cases.json", tmp_path / "out.json"
-    cin.write_text(json.dumps(cases))
-    subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "stft_cases.js"), str(cin), str(cout)], check=True, timeout=120)
-    return json.loads(cout.read_text())
+    return js_host.run_cases("stft_cases.js", cases, tmp_path, tail=0)[0]
 
 
 def window(kind, n):

@@ -164,5 +164,7 @@ def test_js_declarations_match_hilbert_exports():
     assert re.search(r"export const hilbert: \{\s*hilbert: typeof hilbertNs\.hilbert;\s*envelope: typeof "
                      r"hilbertNs\.envelope;\s*instantaneousPhase: typeof hilbertNs\.instantaneousPhase;\s*\};", idx)
     js = open(os.path.join(JS, "index.js")).read()
-    assert re.search(r"defineProperty\(module\.exports, 'hilbert', \{\s*value: \{ hilbert: hilbert\.hilbert, envelope: "
-                     r"hilbert\.envelope, instantaneousPhase: hilbert\.instantaneousPhase \},\s*enumerable: false,", js)
+    assert re.search(r"\['hilbert', \{ hilbert: hilbert\.hilbert, envelope: hilbert\.envelope, instantaneousPhase: "
+                     r"hilbert\.instantaneousPhase \}\],", js)   # a row of the table of non-enumerable sub-modules
+    assert re.search(r"for \(const \[name, value\] of hidden\) Object\.defineProperty\(module\.exports, name, \{ value, "
+                     r"enumerable: false \}\);", js)

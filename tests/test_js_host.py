@@ -11,20 +11,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import js_host
 from conftest import rel_err
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADDON = os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.node")
-NODE = shutil.which("node")
-needs_node = pytest.mark.skipif(NODE is None or not os.path.exists(ADDON), reason="node or the addon is not available")
+from js_host import NODE, ROOT, needs_node
 
 
 def run_cases(cases, tmp_path):
-    cin, cout = tmp_path / "cases.json", tmp_path / "out.json"
-    cin.write_text(json.dumps(cases))
-    subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "run_cases.js"), str(cin), str(cout)],
-                   check=True, timeout=120)
-    return json.loads(cout.read_text())
+    return js_host.run_cases("run_cases.js", cases, tmp_path, tail=0)[0]
 
 
 @needs_node

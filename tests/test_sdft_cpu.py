@@ -71,8 +71,9 @@ def test_js_declarations_match_sdft_exports():
     assert re.search(r"export const sdft: \{\s*slidingDft: typeof sdftNs\.slidingDft;\s*goertzel: typeof "
                      r"sdftNs\.goertzel;\s*\};", idx)
     js = open(os.path.join(JS, "index.js")).read()
-    assert re.search(r"defineProperty\(module\.exports, 'sdft', \{\s*value: \{ slidingDft: sdft\.slidingDft, goertzel: "
-                     r"sdft\.goertzel \},\s*enumerable: false,", js)
+    assert re.search(r"\['sdft', \{ slidingDft: sdft\.slidingDft, goertzel: sdft\.goertzel \}\],", js)   # a row of the table
+    assert re.search(r"for \(const \[name, value\] of hidden\) Object\.defineProperty\(module\.exports, name, \{ value, "
+                     r"enumerable: false \}\);", js)
     napi = open(os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_napi.c")).read()
     assert '{"sdft", Sdft}' in napi and "pdsp_sdft_host_f64(" in napi
 
