@@ -37,6 +37,7 @@ from .resample import (  # noqa: F401
 from .wavelet import Dwt, wavedec, wavedecHost, wavelet_taps, waverec, waverecHost  # noqa: F401
 from .ntt import NTT_MODULUS, Ntt, convolve_exact, intt, ntt, ntt_mul, ntt_root, polymul  # noqa: F401
 from .sdft import SlidingDft, goertzel, sliding_dft  # noqa: F401
+from .fft2d import Fft2d, fft2, ifft2  # noqa: F401
 
 __all__ = [
     "ComplexArray", "Radix2Fft", "createComplexArray", "isPowerOfTwo", "nextPowerOfTwo",
@@ -49,4 +50,5 @@ __all__ = [
     "Dwt", "wavedec", "waverec", "wavedecHost", "waverecHost", "wavelet_taps",
     "Ntt", "ntt_mul", "ntt", "intt", "polymul", "convolve_exact", "NTT_MODULUS", "ntt_root",
     "SlidingDft", "sliding_dft", "goertzel",
+    "Fft2d", "fft2", "ifft2",
 ]

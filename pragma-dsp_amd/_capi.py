@@ -230,6 +230,22 @@ def _load() -> C.CDLL:
         fn.argtypes = args
         fn.restype = res
     lib._pdsp_symbols = tuple(sigs)
+    # include/pdsp_hip_fft2d.h: a header of its own, bound from a table of its own onto the same library
+    fft2d_sigs = {
+        "pdsp_fft2d_create": ([ll, ll, i32, C.POINTER(vp)], i32),
+        "pdsp_fft2d_destroy": ([vp], i32),
+        "pdsp_fft2d_height": ([vp], ll),
+        "pdsp_fft2d_width": ([vp], ll),
+        "pdsp_fft2d_c2c_f32": ([vp, ll, vp, vp, vp, vp, i32, i32, vp], i32),
+        "pdsp_fft2d_c2c_f64": ([vp, ll, vp, vp, vp, vp, i32, i32, vp], i32),
+        "pdsp_fft2d_host_f64": ([dp, dp, ll, ll, ll, i32, i32, dp, dp], i32),
+        "pdsp_fft2d_query": ([ll, ll, i32, C.POINTER(i32)], i32),
+    }
+    for name, (args, res) in fft2d_sigs.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = res
+    lib._pdsp_fft2d_symbols = tuple(fft2d_sigs)
     return lib
 
 

@@ -1,6 +1,6 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from fourteen translation units so that (i) the kernels compile in parallel and
+// dispatchers.  The library is built from fifteen translation units so that (i) the kernels compile in parallel and
 // (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
 // chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
 //   pdsp_capi.hip                 host side + extern "C"
@@ -17,6 +17,7 @@
 //   pdsp_kernels_czt.hip          chirp-z transform and zoom FFT (czt / zoom_fft), f32 and f64
 //   pdsp_kernels_ntt.hip          number-theoretic transform and exact convolution over GF(2^64 - 2^32 + 1)
 //   pdsp_kernels_sdft.hip         sliding DFT (chosen bins at every hop), f32 and f64
+//   pdsp_kernels_fft2d.hip        2-D transform of images (fft2 / ifft2), f32 and f64
 // The dispatchers themselves are pdsp_dispatch.inc (templates on the scalar type), explicitly instantiated there.
 // Not part of the boundary: nothing outside pragma-dsp_amd/csrc includes this file.
 #pragma once
@@ -33,6 +34,7 @@
 
 #include "../../include/pdsp_hip.h"
 #include "../../include/pdsp_hip_dev.h"
+#include "../../include/pdsp_hip_fft2d.h"
 #include "pdsp_fft_core.h"
 
 namespace pdsp_host {
@@ -434,5 +436,39 @@ template <typename T>
 int sdft_dev(long long n, long long hop, int nbins, int ncomp, const double *weights, long long batch, const T *in,
              long long in_stride, long long samples, T *re_out, T *im_out, long long out_stride,
              const typename pdsp::vec2<T>::type *tab, hipStream_t s);
+
+// pdsp_fft2d_* after validation (pdsp_kernels_fft2d.hip).  The one decision of the family, shared by the launch code and
+// pdsp_fft2d_query: H and W powers of two, 16 <= H <= 512, 16 <= W <= the single-pass row limit of the precision.
+//   H*W <= 4096: resident -- one launch, `images` = 4096 / (H*W) whole images per 256-thread workgroup;
+//   else two passes -- the W-plan's row kernels, then one column launch on tiles of `tile` adjacent columns of one
+//   image: 256 (one thread per column) at H = 16, 32; at H >= 64 segments of at least 128 bytes where W allows it --
+//   64 columns at H = 64 and 32 at H = 128 (one round of the workgroup's LDS rows), 32 (f32) / 16 (f64) at H = 256 and
+//   512 (the LDS that fits; at H = 512 in f32 32 columns in one workgroup per CU measured 6-12 % ahead of 16 in two:
+//   DESIGN.md 4.18, profiles/fft2d_tile512_ab.txt) -- and never wider than W.
+#ifndef PDSP_FFT2D_TILE512_F32
+#define PDSP_FFT2D_TILE512_F32 32  /* columns per tile at H = 512 in f32: 32 (139,776 B of LDS, one workgroup per CU) or 16 (69,888 B, two); A/B builds: make EXTRA=-DPDSP_FFT2D_TILE512_F32=16 */
+#endif
+struct Fft2dPath {
+  bool resident = false;
+  int images = 0, tile = 0, launches = 0;
+};
+inline bool fft2d_path(long long h, long long w, size_t elem, Fft2dPath *out) {
+  const long long wmax = 1LL << (elem == 4 ? pdsp::kMaxLog2N_f32 : pdsp::kMaxLog2N_f64);
+  if ((elem != 4 && elem != 8) || h < 16 || h > 512 || w < 16 || w > wmax || (h & (h - 1)) || (w & (w - 1))) return false;
+  Fft2dPath p;
+  if (h * w <= 4096) {
+    p.resident = true, p.images = (int)(4096 / (h * w)), p.launches = 1;
+  } else {
+    const long long wide = h <= 32 ? 256 : h == 64 ? 64 : h == 128 ? 32 : elem == 8 ? 16 : h == 256 ? 32 : PDSP_FFT2D_TILE512_F32;
+    p.tile = (int)(wide < w ? wide : w), p.launches = 2;
+  }
+  *out = p;
+  return true;
+}
+// plan_w / plan_h: the plans of W and H points on the handle's device (made current by the caller); im_in null: real
+// images; forward kernels only (the caller swaps planes for the inverse); scale: the norm's, applied in the last store
+template <typename T>
+int fft2d_dev(const Fft2dPath &path, const pdsp_plan *plan_w, const pdsp_plan *plan_h, long long batch, const T *re_in,
+              const T *im_in, T *re_out, T *im_out, T scale, hipStream_t s);
 
 }  // namespace pdsp_host
