@@ -1,9 +1,17 @@
 // pdsp_internal.h -- what the translation units of libpdsp_hip.so share: the plan object and its device tables,
 // error reporting, the stream-ordered scratch pool, the development switches, and the DECLARATIONS of the kernel
-// dispatchers.  The library is built from fifteen translation units so that (i) the kernels compile in parallel and
-// (ii) a change to the host side of the boundary (pdsp_capi.hip: validation, plan tables, caches, staging, the
-// chunked host calls, the extern "C" entry points -- no kernel is instantiated there) does not recompile them:
-//   pdsp_capi.hip                 host side + extern "C"
+// dispatchers.  This header is the contract between the two kinds of translation unit the library is built from, cut
+// so that (i) the kernels compile in parallel and (ii) a change to the host side of the boundary (the pdsp_capi*.hip
+// units: validation, plan tables, caches, staging, the chunked host calls, the extern "C" entry points -- no kernel
+// is instantiated there) does not recompile them.  The host units, which share pdsp_host.h (no kernel unit includes
+// it), mirror the kernel units family by family:
+//   pdsp_capi.hip                 the core: error state, scratch pools, plans and the plan cache, windows, planes,
+//                                 the device-pointer transforms, spectra and element-wise entry points; it defines
+//                                 what pdsp_host.h declares
+//   pdsp_capi_host.hip            the f64 drop-in: the chunked host calls of transforms and spectra
+//   pdsp_capi_fir.hip, _stft, _dct, _hilbert, _resample, _chirp (DFT and CZT), _dwt, _ntt, _sdft, _fft2d
+//                                 one family each: validators, handle, entry points, host form, switches and queries
+// The kernel units:
 //   pdsp_kernels_f32_fft.hip      run_complex<float>, run_interleaved<float>, element-wise f32 kernels
 //   pdsp_kernels_f32_spectrum.hip spectrum_impl<float> (fused spectrum kernels, findPeak kernels)
 //   pdsp_kernels_f64.hip          every dispatcher for double
@@ -162,7 +170,7 @@ struct Tables {
   float *hp_win = nullptr;  // angle-addition tables of the fused cosine-sum windows (TileGeom::wa ...): wa | wb | wstep | we | wq
   size_t hp_win_a = 0;      // entries (cos, sin pairs) of wa
   // every device allocation made for this precision, the lazily built win[] entries included (upload_table in
-  // pdsp_capi.hip is the one place that adds to it).  Touched under plan->mu or before the plan is published only.
+  // pdsp_host.h is the one place that adds to it).  Touched under plan->mu or before the plan is published only.
   std::vector<void *> owned;
   size_t owned_bytes = 0;  // of `owned`, for the live counters
   void release() {
@@ -261,7 +269,7 @@ inline int check_plan_batch(const pdsp_plan *plan, long long batch) {
 }
 
 // Byte ranges, not pointer equality: do [a, a + a_bytes) and [b, b + b_bytes) share a byte?  A null pointer or an empty
-// range shares none.  (pdsp_capi.hip's argument checks and pdsp_dispatch.inc's.)
+// range shares none.  (The argument checks of the pdsp_capi*.hip units and pdsp_dispatch.inc's.)
 inline bool host_ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
   const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
   return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;

@@ -1,5 +1,5 @@
 // Kernel unit: the chirp-z transform and zoom FFT of rows (pdsp_czt_kernel.h), f32 and f64.
-// See pdsp_internal.h.  The callers in pdsp_capi.hip have validated every argument.
+// See pdsp_internal.h.  The callers in pdsp_capi_chirp.hip have validated every argument.
 #include "pdsp_internal.h"
 #include "pdsp_czt_kernel.h"
 

@@ -1,5 +1,5 @@
 // Kernel unit: DCT-II and DCT-III of rows (pdsp_dct_kernel.h), f32 and f64.
-// See pdsp_internal.h.  The callers in pdsp_capi.hip have validated every argument.
+// See pdsp_internal.h.  The callers in pdsp_capi_dct.hip have validated every argument.
 #include "pdsp_internal.h"
 #include "pdsp_dct_kernel.h"
 

@@ -1,5 +1,5 @@
 // Kernel unit: the any-length DFT of rows by Bluestein's chirp-z algorithm (pdsp_bluestein_kernel.h), f32 and f64.
-// See pdsp_internal.h.  The callers in pdsp_capi.hip have validated every argument.
+// See pdsp_internal.h.  The callers in pdsp_capi_chirp.hip have validated every argument.
 #include "pdsp_internal.h"
 #include "pdsp_bluestein_kernel.h"
 

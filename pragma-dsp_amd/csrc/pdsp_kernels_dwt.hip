@@ -1,5 +1,5 @@
 // Kernel unit: the multi-level wavelet transform of real rows (pdsp_dwt_kernel.h), f32 and f64, and the rule that
-// chooses the path and sizes a tile.  See pdsp_internal.h.  The callers in pdsp_capi.hip have validated every argument.
+// chooses the path and sizes a tile.  See pdsp_internal.h.  The callers in pdsp_capi_dwt.hip have validated every argument.
 #include "pdsp_internal.h"
 #include "pdsp_dwt_kernel.h"
 

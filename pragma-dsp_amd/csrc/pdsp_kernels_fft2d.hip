@@ -1,5 +1,5 @@
 // Kernel unit: the 2-D transform of images (pdsp_fft2d_kernel.h), f32 and f64.  See pdsp_internal.h.  The callers in
-// pdsp_capi.hip have validated every argument; `path` is fft2d_path()'s answer for this shape and precision.
+// pdsp_capi_fft2d.hip have validated every argument; `path` is fft2d_path()'s answer for this shape and precision.
 #include "pdsp_internal.h"
 #include "pdsp_fft2d_kernel.h"
 

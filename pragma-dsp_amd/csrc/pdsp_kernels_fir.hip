@@ -1,5 +1,5 @@
 // Kernel unit: FIR filtering by fused overlap-save (pdsp_fir_kernel.h) and the filter spectrum, f32 and f64.
-// See pdsp_internal.h.  The callers in pdsp_capi.hip have validated every argument.
+// See pdsp_internal.h.  The callers in pdsp_capi_fir.hip have validated every argument.
 #include "pdsp_internal.h"
 #include "pdsp_fir_kernel.h"
 

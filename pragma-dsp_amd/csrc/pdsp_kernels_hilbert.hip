@@ -1,5 +1,5 @@
 // Kernel unit: the Hilbert transform of rows and the analytic signal's parts (pdsp_hilbert_kernel.h), f32 and f64.
-// See pdsp_internal.h.  The callers in pdsp_capi.hip have validated every argument.
+// See pdsp_internal.h.  The callers in pdsp_capi_hilbert.hip have validated every argument.
 #include "pdsp_internal.h"
 #include "pdsp_hilbert_kernel.h"
 

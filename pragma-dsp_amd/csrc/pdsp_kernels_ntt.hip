@@ -1,5 +1,5 @@
 // Kernel unit: the number-theoretic transform over GF(2^64 - 2^32 + 1), its inverse, the fused exact convolution and the
-// element-wise product (pdsp_ntt_kernel.h).  See pdsp_internal.h.  The callers in pdsp_capi.hip have validated every
+// element-wise product (pdsp_ntt_kernel.h).  See pdsp_internal.h.  The callers in pdsp_capi_ntt.hip have validated every
 // argument.
 #include "pdsp_internal.h"
 #include "pdsp_ntt_kernel.h"

@@ -1,5 +1,5 @@
 // Kernel unit: polyphase rate change of real rows (pdsp_upfirdn_kernel.h), f32 and f64, and the rule that sizes a
-// tile.  See pdsp_internal.h.  The callers in pdsp_capi.hip have validated every argument.
+// tile.  See pdsp_internal.h.  The callers in pdsp_capi_resample.hip have validated every argument.
 #include "pdsp_internal.h"
 #include "pdsp_upfirdn_kernel.h"
 

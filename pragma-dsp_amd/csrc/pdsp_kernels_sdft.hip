@@ -1,5 +1,5 @@
 // Kernel unit: the sliding DFT of rows (pdsp_sdft_kernel.h), f32 and f64.
-// See pdsp_internal.h.  The callers in pdsp_capi.hip have validated every argument.
+// See pdsp_internal.h.  The callers in pdsp_capi_sdft.hip have validated every argument.
 #include <cstdlib>
 
 #include "pdsp_internal.h"

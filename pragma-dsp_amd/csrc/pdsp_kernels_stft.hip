@@ -1,5 +1,5 @@
 // Kernel unit: the complex short-time transform and its overlap-add inverse (pdsp_stft_kernel.h), f32 and f64.
-// See pdsp_internal.h.  The callers in pdsp_capi.hip have validated every argument.
+// See pdsp_internal.h.  The callers in pdsp_capi_stft.hip have validated every argument.
 #include "pdsp_internal.h"
 #include "pdsp_stft_kernel.h"
 

@@ -201,7 +201,7 @@ def test_the_generator_reproduces_the_committed_table(pdsp):
     for p in range(1, 11):
         assert np.abs(gen_daubechies.daubechies(p) - pdsp.wavelet_taps(f"db{p}")).max() <= 1e-14, p
     # the table in the host code is the tool's output, line for line
-    src = open(os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_capi.hip")).read()
+    src = open(os.path.join(ROOT, "pragma-dsp_amd", "csrc", "pdsp_capi_dwt.hip")).read()
     assert gen_daubechies.table() in src
 
 

@@ -1,4 +1,4 @@
-"""Batched host-f64 calls large enough to be cut into chunks on several workers (pdsp_capi.hip, run_chunked):
+"""Batched host-f64 calls large enough to be cut into chunks on several workers (pdsp_capi_host.hip, run_chunked):
 pdsp_spectrum_batch_host_f64 -- what the JS drop-in's spectrumBatch() binds, the map of the reference's
 spectrumStream (src/effect/index.ts:190-194) -- and pdsp_fft_transform_host_f64 on many rows
 (Radix2Fft.transform, src/core/fft.ts:89-151).  The chunked result must equal the one-shot sequence

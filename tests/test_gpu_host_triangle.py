@@ -1,7 +1,7 @@
 """The promise of the batched host-f64 forms, as a triangle per size class: the chunked call == the one-shot sequence
 (PDSP_HOST_THREADS=1) == the one-row calls, bit for bit -- pdsp_fft_transform_host_f64 / _rows_host_f64 and the three
 batched spectrum forms against pdsp_spectrum_host_f64.  "Row b of the result is the one-shot result of row b" (above
-kChunkInBytes in pdsp_capi.hip) and "Element i equals forward(inputs[i])" (core.py, js/core.js) hold only if the kernel
+kChunkInBytes in pdsp_capi_host.hip) and "Element i equals forward(inputs[i])" (core.py, js/core.js) hold only if the kernel
 variant of a row never depends on how many rows travel with it, in the call or in a chunk of it.
 
 The size classes come from the library: pdsp_dev_transform_path_f64 / _f32 over log2 N = 1 ... 18 / 19 for real, complex
@@ -12,7 +12,7 @@ are cut into chunks plus a few rows, so that the last chunk is shorter than the 
 hand); at N = 16384 also the batches around the device forms' 8-row threshold for f64 real rows (20 rows: every chunk
 below it; 67: chunks of 8 and a tail of 3; 8 and 7 rows).
 
-host_cut() mirrors chunk_in_bytes / host_workers / transform_cut / spectrum_cut of pdsp_capi.hip; every case asserts the
+host_cut() mirrors chunk_in_bytes / host_workers / transform_cut / spectrum_cut of pdsp_capi_host.hip; every case asserts the
 regime it names (chunked or not, rows per chunk, rows in the tail) on the mirror, and the mirror against the library's own
 answer (pdsp_dev_host_transform_chunks / pdsp_dev_host_spectrum_chunks).  Every comparison of results is np.array_equal on
 outputs pre-filled with NaN; the oracle is held on a few rows at the tolerances of test_gpu_host_chunked.py."""
@@ -36,7 +36,7 @@ MAX_LOG2 = {64: 18, 32: 19}
 SINGLE_PASS_LOG2 = {64: 13, 32: 14}  # kMaxLog2N_f64 / _f32: above, transforms run on the multi-pass paths
 THREADS = (2, 6)
 
-# ---- the cut, restated (pdsp_capi.hip) ------------------------------------------------------------------------------
+# ---- the cut, restated (pdsp_capi_host.hip) ------------------------------------------------------------------------
 CHUNK_IN_BYTES = 2 << 20
 CHUNKED_MIN_BYTES = 4 << 20
 

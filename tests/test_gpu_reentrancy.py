@@ -506,7 +506,7 @@ def closed_cases():
 
 @pytest.mark.parametrize("name", ["BatchedFft", "Resampler", "Upfirdn", "Dft", "Czt", "Dwt", "Ntt", "SlidingDft"])
 def test_e_a_closed_handle_refuses_every_call(name):
-    """Every entry point that takes a handle checks it for null before anything else (pdsp_capi.hip: check_plan_batch,
+    """Every entry point that takes a handle checks it for null before anything else (the pdsp_capi*.hip units: check_plan_batch,
     check_packed_plan, upfirdn_t, dft_t, czt_t, dwt_t, ntt_t, sdft_t, pdsp_plan_window_*), and close() leaves the
     Python object with a null handle: a call after close() is an argument error, not a crash."""
     make, calls = closed_cases()[name]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Daubechies' extremal-phase scaling filters db1 ... db10, as the f64 table of pragma-dsp_amd/csrc/pdsp_capi.hip
+"""Daubechies' extremal-phase scaling filters db1 ... db10, as the f64 table of pragma-dsp_amd/csrc/pdsp_capi_dwt.hip
 (kDaubechies).  numpy only.
 
 For p vanishing moments: P(y) = sum_{k < p} C(p - 1 + k, k) y^k is the polynomial with
